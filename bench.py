@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: CSTP pre-training clips/s on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]   (N > 1: launched by torch.distributed.run)
 
 A "step" is one full optimisation step of the hot path on one resident synthetic batch:
 4 encoder forwards (2 online + 2 target), EMA, heads, losses, 2 encoder backwards, DDP gradient
@@ -28,6 +28,7 @@ Prints ONE JSON line on rank 0.  Besides the contract's fields:
 from __future__ import annotations
 
 import argparse
+import copy
 import ctypes
 import json
 import os
@@ -160,6 +161,31 @@ def conv_work(n, c, d, h, w, k, kt, kh, kw, st, sh, sw, pt, ph, pw):
     return flops, nbytes
 
 
+DUMP_SAMPLE = 1 << 20           # elements kept per arena by --dump-outputs (4 MB each in float32)
+
+
+def dump_outputs(out_dir, out, arenas):
+    """--dump-outputs: what the last timed step computed, as float32 .npy files -- what PretrainStep returns (the losses,
+    the gradient norm, the six heads' logits) and the state it updated (parameters, gradients, EMA target, BatchNorm
+    running statistics: whole when small, else a fixed, seeded sample of DUMP_SAMPLE elements, the same indices in every
+    run of the same model).  Called right after the timed region, before the extra steps overwrite any of it."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss_total": out.loss_total, "loss_byol": out.loss_byol, "ce": torch.stack(list(out.ce)),
+              "grad_norm": out.grad_norm, "ntxent": out.ntxent}
+    arrays.update({"logits_%d" % i: l for i, l in enumerate(out.logits)})
+    g = torch.Generator().manual_seed(0)
+    for name in ("param", "grad", "target", "buffers"):
+        a = arenas[name]
+        if a.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, a.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            a = a[idx.to(a.device)]
+        arrays[name] = a
+    for name, t in arrays.items():
+        if t is not None:
+            np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -170,7 +196,10 @@ def main():
     ap.add_argument("--depth", type=int, default=DEPTH)
     ap.add_argument("--batch", type=int, default=B_LOCAL)
     ap.add_argument("--frames", type=int, default=T, help="clip length (BASELINE configs[3] uses 32)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -205,6 +234,14 @@ def main():
         ddp = torch.nn.parallel.DistributedDataParallel(model, device_ids=[local_rank], output_device=local_rank,
                                                         find_unused_parameters=False)
     opt = FlatSGD(model.parameters(), lr=0.09, momentum=0.9, weight_decay=5e-4, arenas=arenas)
+    # --dump-outputs: the seeded initial state, restored right before the last timed step.  The weight gradients are summed
+    # with float atomics, so two runs drift apart over many steps on one batch; from this state the last step's inputs are
+    # the same in every run.  Four device copies (~0.1 ms), inside the timed window: a second window would cost a pipeline
+    # refill (~1 ms).
+    state0 = opt_state0 = None
+    if args.dump_outputs:
+        state0 = {k: arenas[k].clone() for k in ("param", "target", "buffers", "nbt_all")}
+        opt_state0 = copy.deepcopy(opt.state_dict())
     ntx = NTXentLoss(device=dev, batch_size=args.batch * world, temperature=0.5, use_cosine_similarity=True)
     step = PretrainStep(ddp, opt, LOSS_WEIGHT, clip_grad_norm=True, ntxent=ntx, ntxent_weight=NTXENT_WEIGHT)
     x1, x2, lab = device_batch(args.batch, args.frames, HW, dev, seed=1 + rank)
@@ -224,18 +261,24 @@ def main():
     timers = KernelTimers(specs, torch.cuda.current_stream().cuda_stream)
     ops.kernel_timer = timers
 
-    def run(n):
-        for _ in range(n):
+    def run(n, restore_last=False):
+        out = None
+        for i in range(n):
+            if restore_last and i == n - 1:
+                for k, v in state0.items():
+                    arenas[k].copy_(v)
+                opt.load_state_dict(opt_state0)      # no momentum yet: the SGD kernel's first-step branch
             out = step(x1, x2, lab["spa"], lab["tem"], lab["pb"], lab["rot1"], lab["rot2"])
             lagged.push(out)                     # the driver's per-iteration log read: no host sync (one step late)
         lagged.flush()
+        return out
 
-    def timed_loop(n):
+    def timed_loop(n, restore_last=False):
         if launched:
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        run(n)
+        out = run(n, restore_last)
         torch.cuda.synchronize()
         if launched:
             dist.barrier()
@@ -244,13 +287,15 @@ def main():
             tt = torch.tensor([el], dtype=torch.float64, device=dev)
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             el = float(tt)
-        return el
+        return el, out
 
     run(1)                # untimed: first sight of every layer geometry reads (or times) its tile
     run(args.warmup)
     timers.enabled = {"S1 fwd"}
-    elapsed = timed_loop(args.steps)
+    elapsed, last = timed_loop(args.steps, restore_last=state0 is not None)
     timers.enabled = set()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, arenas)
 
     lib = _lib.load()
     default_terms = lib.cstp_gemm_get_split_terms()
@@ -328,7 +373,7 @@ def main():
                 continue
             ops.set_split_terms(terms)
             run(2)                                                # tiles of this arithmetic + one warm step
-            el = timed_loop(3)
+            el, _ = timed_loop(3)
             arith[label] = args.batch * 3 / el
         ops.set_split_terms(0)
         arith["note"] = ("clips/s of the identical step in this process; `value` is the first entry; 3 timed steps each for "
