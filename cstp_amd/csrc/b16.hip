@@ -15,7 +15,10 @@
 //   conv_b16_kernel<MT, TAB>   implicit GEMM, forward AND data gradient: tile = 128 positions x 16*MT channels, K-tile 32,
 //                              X gathered with 2-byte buffer loads (halo = out-of-range offset = 0), both operands through a
 //                              swizzled LDS double buffer, one barrier per K-tile.  TAB: reduction index k = tap * C + c over a
-//                              zero-padded copy with a per-k offset table (the 3-channel 7x7x7 stem).
+//                              zero-padded copy with a per-k offset table (the 3-channel stems: more than 27 taps).
+//   conv_b16_kernel<.., RAG>   channel counts that are not multiples of 16 under <= 27 taps (R(2+1)D's mid channels): the
+//                              16-channel groups per tap round up, the missing channels of the last one load as zero and the
+//                              pack pads every tap's k to a multiple of 16 with zero weights -- no padded activation copy.
 //   wgrad_b16_kernel<TAB>      dW[m][k] += sum_p dY[m][p] * Xcol[k][p]: 64 x 64 tile, reduction over 64-position chunks,
 //                              split over the positions; every split leaves an fp32 slab, b16_wgrad_reduce_kernel sums them in a
 //                              fixed order into dw[m][c][tap] (deterministic; no atomics).
@@ -90,11 +93,12 @@ pad_b16_kernel(const u16* __restrict__ x, u16* __restrict__ xp, int planes, int 
 }
 
 // ---- weights: fp32 [kout][cin][taps] -> bf16 GEMM operand rows ------------------------------------------------------------------
-// forward:        wp[m = kout (Mp rows)][k = tap * cin + c  (Kw, zero beyond taps * cin)]
-// data gradient:  wp[m = cin  (Mp rows)][k = tap * kout + ko]
+// forward:        wp[m = kout (Mp rows)][k = tap * ip + c  (Kw, zero beyond taps * ip)]
+// data gradient:  wp[m = cin  (Mp rows)][k = tap * ip + ko]
+// (ip: the reduction's channel count, rounded up to 16 for the ragged gather -- zero weights in the padded k; pack_b16.h)
 __global__ void __launch_bounds__(256)
-pack_w_b16_kernel(const float* __restrict__ w, u16* __restrict__ wp, int kout, int cin, int ntaps, int Mp, int Kw, int dgrad) {
-  pack_w_b16_body(w, wp, kout, cin, ntaps, Mp, Kw, dgrad, (int)blockIdx.x, (int)gridDim.x);
+pack_w_b16_kernel(const float* __restrict__ w, u16* __restrict__ wp, int kout, int cin, int ntaps, int Mp, int Kw, int dgrad, int ip) {
+  pack_w_b16_body(w, wp, kout, cin, ntaps, Mp, Kw, dgrad, ip, (int)blockIdx.x, (int)gridDim.x);
 }
 
 // ---- implicit-GEMM convolution, forward and data gradient ---------------------------------------------------------------------
@@ -111,6 +115,7 @@ struct B16Conv {
   int ost, osh, osw, ozt, ozh, ozw;  // output coordinate = q * os + oz
   int ntaps;                       // entries of the tap list (grouped mode), or taps of the table mode
   int Kw;                          // elements per packed weight row
+  int Cw;                          // grouped / PW modes: packed k per tap entry = Cs, or Cs rounded up to 16 (RAG)
   int contig;                      // four consecutive q are four consecutive, 8-byte aligned outputs of one sample
   int n_tiles_x, n_tiles_m;
   int acc;                         // data gradient: out = bf16(bf16(result) + out) -- the sum of a residual connection's two gradients
@@ -135,11 +140,14 @@ __device__ __forceinline__ int b16_slot(int row, int c) { return row * 4 + (c ^ 
 // 4p .. 4p + 3, lane i receives position i of the four rows).
 constexpr int PW_ROW = 18;                           // uint4 per k-row of the PW image: 16 octets of positions + 32 bytes of padding
 
-template <int MT, bool TAB, bool PW = false>
+// RAG (generic gather only): Cs is not a multiple of 16 -- the last 16-channel group of every tap is partial; its channels >= Cs
+// load as zero through an out-of-range offset (as halo positions do) and meet zero weights in the pack (k = tap * Cw + c).
+template <int MT, bool TAB, bool PW = false, bool RAG = false>
 __global__ void __launch_bounds__(256)
 conv_b16_kernel(const B16Conv g, const u16* __restrict__ src, const uint4* __restrict__ wp, u16* __restrict__ out,
                 float* __restrict__ slab, size_t slab_stride) {
   static_assert(!(TAB && PW), "the pointwise mode has no offset table");
+  static_assert(!(RAG && (TAB || PW)), "the ragged channel group is a mode of the generic gather");
   constexpr int BM = 16 * MT;
   constexpr int NW = BM / 64;                       // 16-byte weight chunks per thread and K-tile
   __shared__ uint4 Xs[2][PW ? 32 * PW_ROW : 128 * 4];
@@ -189,7 +197,7 @@ conv_b16_kernel(const B16Conv g, const u16* __restrict__ src, const uint4* __res
   const unsigned nb_off = (unsigned)((size_t)nb * g.Cs * DHWs);          // elements
   const unsigned cstride = (unsigned)DHWs * 2u;                         // bytes between channels
   const __amdgpu_buffer_rsrc_t rs_src = b16_rsrc(src, (unsigned)((size_t)g.Nb * g.Cs * DHWs * 2));
-  const int gpt = (TAB || PW) ? 1 : (g.Cs >> 4);                        // 16-channel groups per tap
+  const int gpt = (TAB || PW) ? 1 : RAG ? ((g.Cs + 15) >> 4) : (g.Cs >> 4);   // 16-channel groups per tap
   const int ngroups = (TAB || PW) ? (g.Kw >> 4) : g.ntaps * gpt;
   const int cblocks = (g.Cs + 31) >> 5;                                 // PW: 32-channel blocks per tap
   const int ntiles_all = PW ? g.ntaps * cblocks : (ngroups + 1) >> 1;
@@ -272,9 +280,16 @@ conv_b16_kernel(const B16Conv g, const u16* __restrict__ src, const uint4* __res
         if ((unsigned)cd < (unsigned)g.Ds && (unsigned)chh < (unsigned)g.Hs && (unsigned)cw < (unsigned)g.Ws)
           vo = (nb_off + (unsigned)(cg * 16) * (unsigned)DHWs + (unsigned)(cd * HWs + chh * g.Ws + cw)) * 2u;
       }
+      if constexpr (RAG) {
+        const int cleft = g.Cs - cg * 16;                                   // channels of my group that exist (wave-uniform)
 #pragma unroll
-      for (int j = 0; j < 16; ++j)
-        xr[j] = (u16)__builtin_amdgcn_raw_buffer_load_b16(rs_src, vo, (unsigned)j * cstride, 0);
+        for (int j = 0; j < 16; ++j)
+          xr[j] = (u16)__builtin_amdgcn_raw_buffer_load_b16(rs_src, j < cleft ? vo : B16_OOB, (unsigned)j * cstride, 0);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+          xr[j] = (u16)__builtin_amdgcn_raw_buffer_load_b16(rs_src, vo, (unsigned)j * cstride, 0);
+      }
     }
     // W
     int kel;                                                            // element offset of my chunk inside the packed row
@@ -282,7 +297,7 @@ conv_b16_kernel(const B16Conv g, const u16* __restrict__ src, const uint4* __res
     if (PW) {
       const int pti = kt / cblocks, cb = kt - pti * cblocks;
       wok = kt < kt_hi && cb * 32 + wc * 8 < g.Cs;
-      kel = taps[(wok ? pti : 0) * 4 + 3] * g.Cs + cb * 32 + wc * 8;
+      kel = taps[(wok ? pti : 0) * 4 + 3] * g.Cw + cb * 32 + wc * 8;
     } else if (TAB) {
       kel = kt * 32 + wc * 8;
       wok = kel < g.Kw;
@@ -290,7 +305,7 @@ conv_b16_kernel(const B16Conv g, const u16* __restrict__ src, const uint4* __res
       const int gi = kt * 2 + (wc >> 1);
       wok = gi < ngroups;
       const int wti = wok ? gi / gpt : 0, wcg = gi - wti * gpt;
-      kel = taps[wti * 4 + 3] * g.Cs + wcg * 16 + (wc & 1) * 8;
+      kel = taps[wti * 4 + 3] * g.Cw + wcg * 16 + (wc & 1) * 8;
     }
     if (PW && g.wf32) {
       // the 1x1x1 forward weight [kout][cin] already IS the row-major GEMM operand: eight floats -> eight bf16 here
@@ -490,7 +505,9 @@ struct B16Wgrad {
   int Nb, Cs, Ds, Hs, Ws;          // x (or its zero-padded copy, TAB) [Nb][Cs][Ds][Hs][Ws]
   int M, Do, Ho, Wo;               // dY [Nb][M][Do][Ho][Wo]
   int st, sh, sw;                  // source coordinate = o * s + off(tap)
-  int ntaps, K;                    // columns: k = tap * Cs + c, K = ntaps * Cs
+  int ntaps, K;                    // columns: k = tap * Cw + c, K = ntaps * Cw
+  int Cw;                          // Cs, or Cs rounded up to 16 (the columns c >= Cs of a ragged group are gathered from whatever
+                                   // lies there -- another channel or an out-of-range zero -- and never read by the reduction)
   int vec8;                        // Do*Ho*Wo % 8 == 0: eight consecutive positions of a dY row are one aligned 16-byte load
   int nchunks, chunks_per_split;   // 64-position chunks
   int kh, kw;
@@ -523,7 +540,7 @@ wgrad_b16_kernel(const B16Wgrad g, const u16* __restrict__ x, const u16* __restr
 
   // X: thread (p, kq) gathers the 16 columns k0 + 16 kq + j of position p
   const int p = t & 63, kq = t >> 6;
-  const int gpt = TAB ? 1 : (g.Cs >> 4);
+  const int gpt = TAB ? 1 : (g.Cw >> 4);
   const int gi = (k0 >> 4) + kq;
   const bool gvalid = TAB ? true : gi < g.ntaps * gpt;
   const int ti = gvalid ? gi / gpt : 0, c0 = (gi - ti * gpt) * 16;
@@ -667,18 +684,18 @@ wgrad_b16_kernel(const B16Wgrad g, const u16* __restrict__ x, const u16* __restr
   }
 }
 
-// dw[m][c][tap] (+)= sum over the S slabs of slab[s][m][k = tap * C + c]   (fixed order: bit-reproducible).
+// dw[m][c][tap] (+)= sum over the S slabs of slab[s][m][k = tap * Cw + c]   (fixed order: bit-reproducible; K = ntaps * Cs).
 // Threads walk dw in ITS order (coalesced read-modify-write); the slab reads of a wave fall on `ntaps` rows of 64-byte lines that
 // the neighbouring waves share (the k-ordered version scattered 4-byte writes 4 * ntaps bytes apart: 2.8 ms per R3D-50 step).
 __global__ void __launch_bounds__(256)
 b16_wgrad_reduce_kernel(const float* __restrict__ slab, int S, size_t stride, float* __restrict__ dw, int M, int Cs, int ntaps, int K,
-                        int Kp, int accumulate) {
+                        int Kp, int accumulate, int Cw) {
   const size_t total = (size_t)M * K;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const int tap = (int)(i % ntaps);
     const size_t r = i / ntaps;
     const int c = (int)(r % Cs), m = (int)(r / Cs);
-    const float* p = slab + (size_t)m * Kp + tap * Cs + c;
+    const float* p = slab + (size_t)m * Kp + tap * Cw + c;
     float a = p[0];
     for (int s = 1; s < S; ++s) a += p[(size_t)s * stride];
     dw[i] = accumulate ? dw[i] + a : a;
@@ -689,7 +706,7 @@ b16_wgrad_reduce_kernel(const float* __restrict__ slab, int S, size_t stride, fl
 // 16 split lanes per block, lane s sums slabs s, s + 16, ... and the 16 partial sums are added in lane order (fixed: reproducible)
 __global__ void __launch_bounds__(256)
 b16_wgrad_reduce_wide_kernel(const float* __restrict__ slab, int S, size_t stride, float* __restrict__ dw, int M, int Cs, int ntaps,
-                             int K, int Kp, int accumulate) {
+                             int K, int Kp, int accumulate, int Cw) {
   __shared__ float red[16][17];
   const int il = threadIdx.x & 15, sl = threadIdx.x >> 4;
   const size_t total = (size_t)M * K;
@@ -699,7 +716,7 @@ b16_wgrad_reduce_wide_kernel(const float* __restrict__ slab, int S, size_t strid
     const int tap = (int)(i % ntaps);
     const size_t r = i / ntaps;
     const int c = (int)(r % Cs), m = (int)(r / Cs);
-    const float* p = slab + (size_t)m * Kp + tap * Cs + c;
+    const float* p = slab + (size_t)m * Kp + tap * Cw + c;
     for (int s = sl; s < S; s += 16) a += p[(size_t)s * stride];
   }
   red[sl][il] = a;
@@ -1210,7 +1227,10 @@ static inline unsigned b16_grid(size_t n, int per_block) {
 
 struct B16Geom {
   int Do, Ho, Wo, ntaps;
-  bool tab;       // reduction over a zero-padded copy with an offset table: channel counts that are not multiples of 16
+  bool tab;       // reduction over a zero-padded copy with an offset table: channel counts that are not multiples of 16 under
+                  // more than 27 taps (the 3-channel stems)
+  int cp, kp;     // c / k, rounded up to 16 where they are not multiples of 16: the packed k per tap of the forward / data gradient
+                  // (ragged counts under <= 27 taps: the generic gather covers the last, partial 16-channel group, RAG)
   int Kw, Dp, Hp, Wp;
 };
 
@@ -1223,9 +1243,11 @@ static bool b16_geom(const cstp_conv_desc* d, B16Geom& q) {
   q.Wo = (d->w + 2 * d->pw - d->kw) / d->sw + 1;
   if (q.Do <= 0 || q.Ho <= 0 || q.Wo <= 0) return false;
   q.ntaps = d->kt * d->kh * d->kw;
-  q.tab = (d->c % 16) != 0;
+  q.tab = (d->c % 16) != 0 && q.ntaps > B16_MAXTAPS;
+  q.cp = q.tab ? d->c : (int)align_up((size_t)d->c, 16);
+  q.kp = (int)align_up((size_t)d->k, 16);
   q.Dp = d->d + 2 * d->pt; q.Hp = d->h + 2 * d->ph; q.Wp = d->w + 2 * d->pw;
-  q.Kw = q.tab ? (int)align_up((size_t)q.ntaps * d->c, 32) : q.ntaps * d->c;
+  q.Kw = q.tab ? (int)align_up((size_t)q.ntaps * d->c, 32) : q.ntaps * q.cp;
   return true;
 }
 
@@ -1247,20 +1269,21 @@ static int b16_conv_split(int blocks0, int ntiles, size_t out_elems) {
 static int b16_fwd_split(const cstp_conv_desc* d, const B16Geom& q) {
   const int BM = d->k > 64 ? 128 : 64;
   const int blocks0 = cdiv(d->n * q.Do * q.Ho * q.Wo, 128) * cdiv(d->k, BM);
-  const int ngroups = q.tab ? q.Kw / 16 : q.ntaps * (d->c / 16);
+  const int ngroups = q.tab ? q.Kw / 16 : q.ntaps * (q.cp / 16);
   return b16_conv_split(blocks0, (ngroups + 1) / 2, (size_t)d->n * d->k * q.Do * q.Ho * q.Wo);
 }
 static int b16_dgrad_split(const cstp_conv_desc* d, const B16Geom& q) {
-  if ((d->k % 16) != 0) return 1;
   const int BM = d->c > 64 ? 128 : 64;
   // the launches of the stride-parity classes run back to back: together they have about the blocks of one un-strided launch
   const int blocks0 = cdiv(d->n * d->d * d->h * d->w, 128) * cdiv(d->c, BM);
   const int taps_class = cdiv(d->kt, d->st) * cdiv(d->kh, d->sh) * cdiv(d->kw, d->sw);
-  return b16_conv_split(blocks0, (taps_class * (d->k / 16) + 1) / 2, (size_t)d->n * d->c * d->d * d->h * d->w);
+  return b16_conv_split(blocks0, (taps_class * (q.kp / 16) + 1) / 2, (size_t)d->n * d->c * d->d * d->h * d->w);
 }
 // weight gradient: positions split over S blocks per tile, each leaving an fp32 slab [M rounded to 64][K rounded to 64]
+// (K = taps x cp: a ragged channel count keeps the padded columns of its last 16-channel group)
+static int b16_wgrad_cols(const cstp_conv_desc* d, const B16Geom& q) { return q.ntaps * (q.tab ? d->c : q.cp); }
 static int b16_wgrad_split(const cstp_conv_desc* d, const B16Geom& q) {
-  const int K = q.ntaps * d->c;
+  const int K = b16_wgrad_cols(d, q);
   const int tiles = cdiv(K, 64) * cdiv(d->k, 64);
   const int nchunks = cdiv(d->n * q.Do * q.Ho * q.Wo, 64);
   int S = cdiv(1536, tiles);
@@ -1275,7 +1298,7 @@ static int b16_wgrad_split(const cstp_conv_desc* d, const B16Geom& q) {
 
 static size_t b16_wpack_bytes(const cstp_conv_desc* d, const B16Geom& q) {
   const size_t mp_f = align_up((size_t)d->k, 128), mp_d = align_up((size_t)d->c, 128);
-  const size_t wf = align_up(mp_f * q.Kw * 2, 256), wd = align_up(mp_d * (size_t)q.ntaps * d->k * 2, 256);
+  const size_t wf = align_up(mp_f * q.Kw * 2, 256), wd = align_up(mp_d * (size_t)q.ntaps * q.kp * 2, 256);
   return wf > wd ? wf : wd;
 }
 
@@ -1286,7 +1309,7 @@ extern "C" size_t cstp_b16_conv3d_workspace_bytes(const cstp_conv_desc* desc) {
   size_t slabs = 0;
   if (sf > 1) slabs = (size_t)sf * desc->n * desc->k * q.Do * q.Ho * q.Wo * sizeof(float);
   if (sd > 1) { const size_t b = (size_t)sd * desc->n * desc->c * desc->d * desc->h * desc->w * sizeof(float); slabs = b > slabs ? b : slabs; }
-  { const size_t b = (size_t)sw * cdiv(desc->k, 64) * 64 * cdiv(q.ntaps * desc->c, 64) * 64 * sizeof(float); slabs = b > slabs ? b : slabs; }
+  { const size_t b = (size_t)sw * cdiv(desc->k, 64) * 64 * cdiv(b16_wgrad_cols(desc, q), 64) * 64 * sizeof(float); slabs = b > slabs ? b : slabs; }
   return b16_wpack_bytes(desc, q) + b16_pad_bytes(desc, q) + align_up(slabs, 256) + 256;
 }
 
@@ -1298,20 +1321,28 @@ extern "C" int cstp_b16_cast(void* stream, const float* x, uint16_t* y, size_t n
   return 0;
 }
 
-template <bool TAB, bool PW = false>
+template <bool TAB, bool PW = false, bool RAG = false>
 static void b16_launch_conv(hipStream_t st, const B16Conv& g, int M, const uint16_t* src, const void* wp, uint16_t* out, float* slab,
                             size_t slab_stride) {
   const int chunk = (g.n_tiles_x + 7) / 8;
   const dim3 grid((unsigned)(8 * chunk * g.n_tiles_m), (unsigned)g.ksplit);
   if (M > 64)
-    hipLaunchKernelGGL((conv_b16_kernel<8, TAB, PW>), grid, dim3(256), 0, st, g, src, reinterpret_cast<const uint4*>(wp), out, slab, slab_stride);
+    hipLaunchKernelGGL((conv_b16_kernel<8, TAB, PW, RAG>), grid, dim3(256), 0, st, g, src, reinterpret_cast<const uint4*>(wp), out, slab, slab_stride);
   else
-    hipLaunchKernelGGL((conv_b16_kernel<4, TAB, PW>), grid, dim3(256), 0, st, g, src, reinterpret_cast<const uint4*>(wp), out, slab, slab_stride);
+    hipLaunchKernelGGL((conv_b16_kernel<4, TAB, PW, RAG>), grid, dim3(256), 0, st, g, src, reinterpret_cast<const uint4*>(wp), out, slab, slab_stride);
+}
+// the generic gather: RAG where the reduction's channel count (the source's) is not a multiple of 16
+static void b16_launch_generic(hipStream_t st, const B16Conv& g, int M, const uint16_t* src, const void* wp, uint16_t* out, float* slab,
+                               size_t slab_stride) {
+  if ((g.Cs % 16) != 0) b16_launch_conv<false, false, true>(st, g, M, src, wp, out, slab, slab_stride);
+  else b16_launch_conv<false>(st, g, M, src, wp, out, slab, slab_stride);
 }
 
-// the octet-gather path (conv_b16_kernel<.., PW>): stride 1, channel counts multiples of 16, 16-byte aligned source, and either
-// 1x1x1 without padding on frames of a multiple of 8 positions (positions are then one linear run per channel), or taps whose
-// column offsets are -1 / 0 / +1 on rows that are multiples of 8 positions in BOTH the source (ws) and the enumerated tensor (wq)
+// the octet-gather path (conv_b16_kernel<.., PW>): stride 1, 16-byte aligned source, and either
+// 1x1x1 without padding on frames of a multiple of 8 positions (positions are then one linear run per channel; channel counts
+// multiples of 16: the forward reads the fp32 weight rows in place), or taps whose column offsets are -1 / 0 / +1 on rows that are
+// multiples of 8 positions in BOTH the source (ws) and the enumerated tensor (wq) -- any channel counts: the gather masks the
+// channels >= Cs of the last 32-channel block, and the pack pads each tap's k to a multiple of 16 (B16Geom::cp / kp)
 static bool b16_pointwise(const cstp_conv_desc* d, const void* src) {
   return d->kt == 1 && d->kh == 1 && d->kw == 1 && d->st == 1 && d->sh == 1 && d->sw == 1 && d->pt == 0 && d->ph == 0 && d->pw == 0 &&
          ((d->d * d->h * d->w) % 8) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 && (d->c % 16) == 0 && (d->k % 16) == 0;
@@ -1319,8 +1350,7 @@ static bool b16_pointwise(const cstp_conv_desc* d, const void* src) {
 static bool b16_octets(const cstp_conv_desc* d, const void* src, int ws, int wq) {
   if (b16_pointwise(d, src)) return true;
   return d->st == 1 && d->sh == 1 && d->sw == 1 && d->kw <= 3 && d->pw <= 1 && d->kw - 1 - d->pw <= 1 &&
-         d->kt * d->kh * d->kw <= B16_MAXTAPS && (ws % 8) == 0 && (wq % 8) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 &&
-         (d->c % 16) == 0 && (d->k % 16) == 0;
+         d->kt * d->kh * d->kw <= B16_MAXTAPS && (ws % 8) == 0 && (wq % 8) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0;
 }
 
 static float* b16_slabs(void* ws, const cstp_conv_desc* d, const B16Geom& q) {
@@ -1333,7 +1363,7 @@ extern "C" int cstp_b16_conv3d_forward(void* stream, const cstp_conv_desc* d, co
   CSTP_REQUIRE(b16_geom(d, q), "bad convolution geometry");
   CSTP_REQUIRE(x && w && y && ws && ws_bytes >= cstp_b16_conv3d_workspace_bytes(d), "null argument or workspace too small");
   CSTP_REQUIRE(q.tab || q.ntaps <= B16_MAXTAPS, "bf16 path: at most 27 filter taps for channel counts that are multiples of 16");
-  CSTP_REQUIRE(!q.tab || q.Kw <= B16_KTAB, "bf16 path: reduction too long for the offset table");
+  CSTP_REQUIRE(!q.tab || q.Kw <= B16_KTAB, "bf16 path: reduction too long for the offset table (more than 27 taps)");
   CSTP_REQUIRE((size_t)d->n * d->c * q.Dp * q.Hp * q.Wp * 2 < (1ull << 31), "bf16 path: gathered tensor must be < 2 GiB");
   CSTP_REQUIRE((reinterpret_cast<uintptr_t>(y) & 7) == 0, "unaligned output");
   hipStream_t st = as_stream(stream);
@@ -1343,8 +1373,8 @@ extern "C" int cstp_b16_conv3d_forward(void* stream, const cstp_conv_desc* d, co
   const bool pw = !q.tab && b16_pointwise(d, x) && (reinterpret_cast<uintptr_t>(w) & 15) == 0;
   if (!pw && !pack_skip(wp)) {      // (pointwise forward: the kernel rounds the fp32 rows itself; pack plan: replayed by the caller)
     const unsigned nb = b16_grid((size_t)Mp * q.Kw, 256);
-    pack_record_b16(w, wp, (int)nb, d->k, d->c, q.ntaps, Mp, q.Kw, 0);
-    hipLaunchKernelGGL(pack_w_b16_kernel, dim3(nb), dim3(256), 0, st, w, wp, d->k, d->c, q.ntaps, Mp, q.Kw, 0);
+    pack_record_b16(w, wp, (int)nb, d->k, d->c, q.ntaps, Mp, q.Kw, 0, q.cp);
+    hipLaunchKernelGGL(pack_w_b16_kernel, dim3(nb), dim3(256), 0, st, w, wp, d->k, d->c, q.ntaps, Mp, q.Kw, 0, q.cp);
     CSTP_LAUNCH_CHECK();
   }
   B16Conv g;
@@ -1355,6 +1385,7 @@ extern "C" int cstp_b16_conv3d_forward(void* stream, const cstp_conv_desc* d, co
   g.M = d->k; g.Do = q.Do; g.Ho = q.Ho; g.Wo = q.Wo;
   g.ost = g.osh = g.osw = 1;
   g.Kw = q.Kw;
+  g.Cw = q.cp;
   g.contig = ((q.Do * q.Ho * q.Wo) % 4) == 0;
   g.n_tiles_x = cdiv(d->n * q.Do * q.Ho * q.Wo, 128);
   g.n_tiles_m = Mp / BM;
@@ -1380,7 +1411,7 @@ extern "C" int cstp_b16_conv3d_forward(void* stream, const cstp_conv_desc* d, co
         }
     if (pw) { g.wf32 = 1; b16_launch_conv<false, true>(st, g, d->k, x, w, y, slab, out_elems); }
     else if (b16_octets(d, x, d->w, q.Wo)) b16_launch_conv<false, true>(st, g, d->k, x, wp, y, slab, out_elems);
-    else b16_launch_conv<false>(st, g, d->k, x, wp, y, slab, out_elems);
+    else b16_launch_generic(st, g, d->k, x, wp, y, slab, out_elems);
   }
   CSTP_LAUNCH_CHECK();
   if (g.ksplit > 1) {
@@ -1400,18 +1431,18 @@ extern "C" int cstp_b16_conv3d_backward_data_acc(void* stream, const cstp_conv_d
   B16Geom q;
   CSTP_REQUIRE(b16_geom(d, q), "bad convolution geometry");
   CSTP_REQUIRE(dy && w && dx && ws && ws_bytes >= cstp_b16_conv3d_workspace_bytes(d), "null argument or workspace too small");
-  CSTP_REQUIRE((d->k % 16) == 0 && q.ntaps <= B16_MAXTAPS, "bf16 data gradient: output channels a multiple of 16, at most 27 taps");
+  CSTP_REQUIRE(q.ntaps <= B16_MAXTAPS, "bf16 data gradient: at most 27 taps");
   CSTP_REQUIRE((size_t)d->n * d->k * q.Do * q.Ho * q.Wo * 2 < (1ull << 31), "bf16 path: gathered tensor must be < 2 GiB");
   CSTP_REQUIRE((reinterpret_cast<uintptr_t>(dx) & 7) == 0, "unaligned output");
   hipStream_t st = as_stream(stream);
   const int BM = d->c > 64 ? 128 : 64;
   const int Mp = (int)align_up((size_t)d->c, BM);
-  const int Kw = q.ntaps * d->k;
+  const int Kw = q.ntaps * q.kp;
   u16* wp = reinterpret_cast<u16*>(ws);
   if (!pack_skip(wp)) {
     const unsigned nb = b16_grid((size_t)Mp * Kw, 256);
-    pack_record_b16(w, wp, (int)nb, d->k, d->c, q.ntaps, Mp, Kw, 1);
-    hipLaunchKernelGGL(pack_w_b16_kernel, dim3(nb), dim3(256), 0, st, w, wp, d->k, d->c, q.ntaps, Mp, Kw, 1);
+    pack_record_b16(w, wp, (int)nb, d->k, d->c, q.ntaps, Mp, Kw, 1, q.kp);
+    hipLaunchKernelGGL(pack_w_b16_kernel, dim3(nb), dim3(256), 0, st, w, wp, d->k, d->c, q.ntaps, Mp, Kw, 1, q.kp);
     CSTP_LAUNCH_CHECK();
   }
   const int ksplit = b16_dgrad_split(d, q);
@@ -1429,6 +1460,7 @@ extern "C" int cstp_b16_conv3d_backward_data_acc(void* stream, const cstp_conv_d
         g.M = d->c; g.Do = d->d; g.Ho = d->h; g.Wo = d->w;
         g.ost = d->st; g.osh = d->sh; g.osw = d->sw; g.ozt = zt; g.ozh = zh; g.ozw = zw;
         g.Kw = Kw;
+        g.Cw = q.kp;
         g.contig = (d->st == 1 && d->sh == 1 && d->sw == 1 && ((d->d * d->h * d->w) % 4) == 0) ? 1 : 0;
         g.n_tiles_x = cdiv(d->n * g.Dq * g.Hq * g.Wq, 128);
         g.n_tiles_m = Mp / BM;
@@ -1446,7 +1478,7 @@ extern "C" int cstp_b16_conv3d_backward_data_acc(void* stream, const cstp_conv_d
         g.ksplit = ksplit;
         g.acc = (accumulate && ksplit <= 1) ? 1 : 0;
         if (b16_octets(d, dy, q.Wo, d->w)) b16_launch_conv<false, true>(st, g, d->c, dy, wp, dx, slab, out_elems);
-        else b16_launch_conv<false>(st, g, d->c, dy, wp, dx, slab, out_elems);
+        else b16_launch_generic(st, g, d->c, dy, wp, dx, slab, out_elems);
         CSTP_LAUNCH_CHECK();
       }
   if (ksplit > 1) {
@@ -1470,8 +1502,10 @@ extern "C" int cstp_b16_conv3d_backward_weight(void* stream, const cstp_conv_des
   g.Nb = d->n; g.Cs = d->c;
   g.M = d->k; g.Do = q.Do; g.Ho = q.Ho; g.Wo = q.Wo;
   g.st = d->st; g.sh = d->sh; g.sw = d->sw;
-  g.ntaps = q.ntaps; g.K = q.ntaps * d->c;
+  g.ntaps = q.ntaps; g.K = b16_wgrad_cols(d, q);
+  g.Cw = q.tab ? d->c : q.cp;
   g.Kp = cdiv(g.K, 64) * 64;
+  const int Kr = q.ntaps * d->c;                   // dw's columns
   const int npo = q.Do * q.Ho * q.Wo;
   g.vec8 = ((npo % 8) == 0 && (reinterpret_cast<uintptr_t>(dy) & 15) == 0) ? 1 : 0;
   g.nchunks = cdiv(d->n * npo, 64);
@@ -1501,12 +1535,12 @@ extern "C" int cstp_b16_conv3d_backward_weight(void* stream, const cstp_conv_des
     else hipLaunchKernelGGL((wgrad_b16_kernel<false>), grid, dim3(256), 0, st, g, x, dy, slab);
   }
   CSTP_LAUNCH_CHECK();
-  if (S >= 16 && (size_t)d->k * g.K <= ((size_t)1 << 20))
-    hipLaunchKernelGGL(b16_wgrad_reduce_wide_kernel, dim3((unsigned)cdiv((int)((size_t)d->k * g.K), 16)), dim3(256), 0, st, slab, S,
-                       slab_stride, dw, d->k, d->c, q.ntaps, g.K, g.Kp, accumulate ? 1 : 0);
+  if (S >= 16 && (size_t)d->k * Kr <= ((size_t)1 << 20))
+    hipLaunchKernelGGL(b16_wgrad_reduce_wide_kernel, dim3((unsigned)cdiv((int)((size_t)d->k * Kr), 16)), dim3(256), 0, st, slab, S,
+                       slab_stride, dw, d->k, d->c, q.ntaps, Kr, g.Kp, accumulate ? 1 : 0, g.Cw);
   else
-    hipLaunchKernelGGL(b16_wgrad_reduce_kernel, dim3(b16_grid((size_t)d->k * g.K, 256)), dim3(256), 0, st, slab, S, slab_stride, dw, d->k,
-                       d->c, q.ntaps, g.K, g.Kp, accumulate ? 1 : 0);
+    hipLaunchKernelGGL(b16_wgrad_reduce_kernel, dim3(b16_grid((size_t)d->k * Kr, 256)), dim3(256), 0, st, slab, S, slab_stride, dw, d->k,
+                       d->c, q.ntaps, Kr, g.Kp, accumulate ? 1 : 0, g.Cw);
   CSTP_LAUNCH_CHECK();
   return 0;
 }

@@ -1137,11 +1137,11 @@ bool pack_skip(const void* dst) {
   return g_prepacked.count(dst) != 0;
 }
 
-void pack_record_b16(const float* w, void* dst, int nblocks, int kout, int cin, int ntaps, int Mp, int Kw, int dgrad) {
+void pack_record_b16(const float* w, void* dst, int nblocks, int kout, int cin, int ntaps, int Mp, int Kw, int dgrad, int ip) {
   if (tl_pack_mode != 1) return;
   cstp_pack_rec r{};
   r.kind = 4; r.nblocks = nblocks; r.w = w; r.dst = dst; r.inv_a = nullptr; r.cells = nullptr;
-  const int a[6] = {kout, cin, ntaps, Mp, Kw, dgrad};
+  const int a[7] = {kout, cin, ntaps, Mp, Kw, dgrad, ip};
   memcpy(r.a, a, sizeof(a));
   tl_pack_recs.push_back(r);
 }
@@ -1204,7 +1204,7 @@ pack_replay_kernel(const cstp_pack_rec* __restrict__ recs, const int* __restrict
   else if (R.kind == 3)
     pack_native_body(R.w, reinterpret_cast<float*>(R.dst), a[0], a[1], a[2], a[3], a[4], a[5], a[6], lb, R.nblocks);
   else
-    pack_w_b16_body(R.w, reinterpret_cast<unsigned short*>(R.dst), a[0], a[1], a[2], a[3], a[4], a[5], lb, R.nblocks);
+    pack_w_b16_body(R.w, reinterpret_cast<unsigned short*>(R.dst), a[0], a[1], a[2], a[3], a[4], a[5], a[6], lb, R.nblocks);
 }
 
 // optional fused input transform of a convolution (see cstp_in_affine in cstp_hip.h); npg = clips per BatchNorm group

@@ -78,14 +78,12 @@ def generate_model(opts):
         else:
             model = R3DBYOL(pretrain=False, cls_bn=True, opts=opts)
     else:
-        if getattr(opts, "act_dtype", "fp32") not in ("fp32", None):
-            raise NotImplementedError("--act_dtype %s: the bf16-storage kernels serve --model_name r3d_byol (BASELINE configs[4]); "
-                                      "r21d_byol runs fp32 storage" % (opts.act_dtype,))
+        act = getattr(opts, "act_dtype", "fp32") or "fp32"
         layer_sizes = layer_sizes_for_depth(opts.model_depth)
         if opts.task in PRETRAIN_TASKS:
-            model = R21DBYOL(pretrain=True, layer_sizes=layer_sizes)
+            model = R21DBYOL(pretrain=True, layer_sizes=layer_sizes, act_dtype=act)
         else:
-            model = R21DBYOL(pretrain=False, num_classes=opts.n_classes, cls_bn=True, layer_sizes=layer_sizes)
+            model = R21DBYOL(pretrain=False, num_classes=opts.n_classes, cls_bn=True, layer_sizes=layer_sizes, act_dtype=act)
     local_rank = opts.local_rank if getattr(opts, "local_rank", -1) not in (-1, None) else 0
     torch.cuda.set_device(local_rank)
     model.cuda(local_rank)

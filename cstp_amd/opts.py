@@ -9,7 +9,7 @@ Additions (all optional, defaults reproduce the reference):
   --max_steps       stop an epoch after this many iterations (0 = full epoch)
   --bucket_cap_mb   DDP gradient bucket size (xGMI ring all-reduce is per-link bound)
   --act_dtype       fp32 (default) | bf16: storage type of the 5-D activations and their gradients (BASELINE configs[4]:
-                    3D-ResNet-50, bf16; --model_name r3d_byol -- cstp_amd/r3d_byol.py)
+                    3D-ResNet-50, bf16; both backbones -- cstp_amd/r3d_byol.py, cstp_amd/r21d_byol.py)
 torchrun passes LOCAL_RANK through the environment instead of --local_rank; both are honoured.
 """
 from __future__ import annotations
@@ -89,7 +89,7 @@ _FLAGS = [
     ("synthetic_len", 256, int, "samples per epoch for --dataset synthetic"),
     ("max_steps", 0, int, "stop each epoch after this many iterations (0 = all)"),
     ("bucket_cap_mb", 25, int, "DDP gradient bucket size in MB"),
-    ("act_dtype", "fp32", str, "fp32 | bf16: activation storage type (bf16: --model_name r3d_byol)"),
+    ("act_dtype", "fp32", str, "fp32 | bf16: activation storage type (r21d_byol and r3d_byol)"),
 ]
 
 

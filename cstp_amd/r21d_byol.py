@@ -14,7 +14,11 @@ all additive:
   * BN+ReLU and BN+residual+ReLU are single kernels; optionally (CSTP_FUSE_BN=1) a BN+ReLU that feeds exactly
     one convolution is folded into that convolution's gather and never materialised;
   * parameters live in flat HBM arenas (``flatten_parameters``) so EMA / clip / SGD are one
-    streaming kernel each instead of ~80 tiny ones (:331-337 rebinding .data per tensor).
+    streaming kernel each instead of ~80 tiny ones (:331-337 rebinding .data per tensor);
+  * ``act_dtype="bf16"`` (--act_dtype bf16): bf16 activation STORAGE, as R3DBYOL has it (r3d_byol.py, include/cstp_hip.h
+    "bf16-STORAGE path"): the clip pair is rounded to bf16 once, every 5-D activation and activation gradient of the encoders is
+    bf16 in HBM -- the mid-channel BatchNorm+ReLU output of each (2+1)D convolution included, which this path materialises --
+    and parameters, gradients, statistics, pooled features, heads, losses, EMA and optimizer stay fp32.
 """
 from __future__ import annotations
 
@@ -219,6 +223,8 @@ class SpatioTemporalConv(nn.Module):
         tensor is never written: -36 % BN traffic, -7 ms/step of BN kernels, -7 GB of activations at cfg2) --
         but the per-element affine costs the MFMA kernels' gather more than the two HBM passes it removes
         (+8 ms/step on MI355X, profiles/r01), so the default materialises BN outputs."""
+        if x.dtype == torch.bfloat16:
+            return self._forward_bf16(x, groups, pre_bn, grad_join)
         if FUSE_BN_INTO_CONV:
             x = self.spatial_conv(x) if pre_bn is None else pre_bn.relu_then(self.spatial_conv, x, groups)
             return self.bn.relu_then(self.temporal_conv, x, groups)
@@ -231,6 +237,15 @@ class SpatioTemporalConv(nn.Module):
                 and _temporal_fused(x, self.temporal_conv, groups)):
             return self.bn.relu_then(self.temporal_conv, x, groups, og, opv)
         return self.temporal_conv(self.bn(x, relu=True, groups=groups), og, opv)
+
+    def _forward_bf16(self, x, groups, pre_bn, grad_join):
+        """bf16 storage: spatial conv -> bf16 BN+ReLU, materialised -> temporal conv.  The fp32 path's fusions have no bf16
+        kernels and are off here by construction, not by a lookup that happens to fail: no BatchNorm folded into a gather
+        (FUSE_BN_INTO_CONV, FUSE_BN_TEMPORAL / in_affine), no statistics from a convolution's epilogue (bn_groups / bn_pivot)."""
+        if pre_bn is not None:
+            x = pre_bn(x, relu=True, groups=groups)
+        x = self.spatial_conv(x, grad_join=grad_join if pre_bn is None else None)
+        return self.temporal_conv(self.bn(x, relu=True, groups=groups))
 
 
 class SpatioTemporalResBlock(nn.Module):
@@ -253,7 +268,8 @@ class SpatioTemporalResBlock(nn.Module):
     def forward(self, x, groups=1):
         # the block's input feeds two ops -- conv1 and the residual addition (or, in a downsample block, conv1 and the shortcut
         # convolution): their two gradients are summed inside the second op's kernel instead of by a separate add pass
-        join = ops.GradJoin(2) if (self.training and torch.is_grad_enabled() and x.requires_grad and not FUSE_BN_INTO_CONV) else None
+        join = ops.GradJoin(2) if (self.training and torch.is_grad_enabled() and x.requires_grad
+                                   and (x.dtype == torch.bfloat16 or not FUSE_BN_INTO_CONV)) else None
         # conv2(relu1(bn1(conv1(x))))
         res = self.conv2(self.conv1(x, groups, grad_join=join, out_bn=self.bn1), groups, pre_bn=self.bn1, out_bn=self.bn2)
         if self.downsample:
@@ -544,8 +560,12 @@ class R21DBYOL(ByolBase):
     """forward(x1, x2, o_type='loss_com') -> (loss_byol, (pred_spa, pred_tem, pred_pb_1, pred_pb_2,
     pred_rot_1, pred_rot_2)) exactly as r21d_byol.py:357-382."""
 
-    def __init__(self, pretrain=True, momentum=0.996, layer_sizes=(1, 1, 1, 1), **kwargs):
+    def __init__(self, pretrain=True, momentum=0.996, layer_sizes=(1, 1, 1, 1), act_dtype="fp32", **kwargs):
         super().__init__()
+        act = act_dtype or "fp32"
+        if act not in ("fp32", "bf16"):
+            raise ValueError("--act_dtype %r: fp32 | bf16" % (act_dtype,))
+        self.act_bf16 = act == "bf16"
         self.pretrain = bool(pretrain)
         self.layer_sizes = tuple(layer_sizes)
         if pretrain:
@@ -586,6 +606,8 @@ class R21DBYOL(ByolBase):
             # online_net(x1); online_net(x2) (r21d_byol.py:359-360) with half the launches, one weight
             # pack per layer and twice the grid on the small deep layers.
             x = torch.cat((x1, x2), dim=0)
+            if self.act_bf16:
+                x = ops.to_bf16(x)             # bf16 storage: ops dispatch on the activation dtype from here on
             if OVERLAP_TARGET_FORWARD and x.is_cuda:
                 # The target network's forward depends on nothing the online forward produces (the EMA reads the online
                 # PARAMETERS, which no forward modifies), so it runs on a second HIP stream: its HBM-bound BatchNorm kernels
@@ -643,7 +665,7 @@ class R21DBYOL(ByolBase):
         elif o_type in ["ft_fc", "ft_all", "test"]:
             if self.pretrain:
                 raise AttributeError("R21DBYOL(pretrain=True) has no classify/cls_bn: o_type=%r needs pretrain=False" % o_type)
-            online_feat = self.online_net(x1)                       # r21d_byol.py:395 (proj_flag False: features only)
+            online_feat = self.online_net(ops.to_bf16(x1) if self.act_bf16 else x1)   # :395 (features only; fp32 either way)
             online_feat = ops.l2_normalize(online_feat)             # F.normalize(p=2, dim=1) :396
             if self.cls_bn is False or self.cls_bn is None:
                 raise TypeError("'bool' object is not callable")    # the reference calls self.cls_bn unconditionally (:397)

@@ -395,9 +395,12 @@ int cstp_adam_step(void* stream, float* p, const float* g, float* exp_avg, float
  * arithmetic between a load and a store is fp32 (fp64 in the BatchNorm reductions), each stored value is rounded to
  * nearest-even once; weights, weight gradients, BatchNorm parameters / statistics stay fp32; convolution operands are the
  * bf16 activations and the fp32 weights rounded to bf16 at use (v_mfma_f32_16x16x32_bf16, fp32 accumulation).
- * Geometry limits: channel counts that are multiples of 16 with at most 27 taps (every layer of the network but the stem), or
- * any channel count with taps * channels <= 1056 (the 3-channel 7x7x7 stem, forward and weight gradient only); every
- * gathered tensor < 2 GiB.  Anything else is refused with an error, not emulated. */
+ * Geometry limits: any channel counts with at most 27 taps -- forward, data gradient and weight gradient (counts that are not
+ * multiples of 16, such as R(2+1)D's mid channels 83 / 230 / 460 / 921, are gathered in 16-channel groups whose last one is
+ * partial: the missing channels read as zero and meet zero-padded packed weights; no padded copy of the activation) -- or, above
+ * 27 taps, any channel count with taps * channels <= 1056 (the 3-channel 7x7x7 / 1x7x7 stems through a zero-padded copy and an
+ * offset table, forward and weight gradient only); every gathered tensor < 2 GiB.  Anything else is refused with an error, not
+ * emulated. */
 /* x.to(torch.bfloat16) of the clip (r3d_byol.py:193-194 under autocast): n floats -> n bf16, round to nearest even. */
 int cstp_b16_cast(void* stream, const float* x, uint16_t* y, size_t n);
 size_t cstp_b16_conv3d_workspace_bytes(const cstp_conv_desc* desc);
