@@ -1371,9 +1371,9 @@ extern "C" int cstp_b16_conv3d_forward(void* stream, const cstp_conv_desc* d, co
   const int Mp = (int)align_up((size_t)d->k, BM);
   u16* wp = reinterpret_cast<u16*>(ws);
   const bool pw = !q.tab && b16_pointwise(d, x) && (reinterpret_cast<uintptr_t>(w) & 15) == 0;
-  if (!pw && !pack_skip(wp)) {      // (pointwise forward: the kernel rounds the fp32 rows itself; pack plan: replayed by the caller)
-    const unsigned nb = b16_grid((size_t)Mp * q.Kw, 256);
-    pack_record_b16(w, wp, (int)nb, d->k, d->c, q.ntaps, Mp, q.Kw, 0, q.cp);
+  // (pointwise forward: the kernel rounds the fp32 rows itself; pack plan: a pack equal to the replayed one is skipped)
+  const unsigned nb = b16_grid((size_t)Mp * q.Kw, 256);
+  if (!pw && !pack_site_b16(w, wp, (int)nb, d->k, d->c, q.ntaps, Mp, q.Kw, 0, q.cp)) {
     hipLaunchKernelGGL(pack_w_b16_kernel, dim3(nb), dim3(256), 0, st, w, wp, d->k, d->c, q.ntaps, Mp, q.Kw, 0, q.cp);
     CSTP_LAUNCH_CHECK();
   }
@@ -1439,9 +1439,8 @@ extern "C" int cstp_b16_conv3d_backward_data_acc(void* stream, const cstp_conv_d
   const int Mp = (int)align_up((size_t)d->c, BM);
   const int Kw = q.ntaps * q.kp;
   u16* wp = reinterpret_cast<u16*>(ws);
-  if (!pack_skip(wp)) {
-    const unsigned nb = b16_grid((size_t)Mp * Kw, 256);
-    pack_record_b16(w, wp, (int)nb, d->k, d->c, q.ntaps, Mp, Kw, 1, q.kp);
+  const unsigned nb = b16_grid((size_t)Mp * Kw, 256);
+  if (!pack_site_b16(w, wp, (int)nb, d->k, d->c, q.ntaps, Mp, Kw, 1, q.kp)) {
     hipLaunchKernelGGL(pack_w_b16_kernel, dim3(nb), dim3(256), 0, st, w, wp, d->k, d->c, q.ntaps, Mp, Kw, 1, q.kp);
     CSTP_LAUNCH_CHECK();
   }

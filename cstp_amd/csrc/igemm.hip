@@ -1001,6 +1001,7 @@ static bool run_linear(hipStream_t s, const cstp_conv_desc& d, bool dgrad, const
   const int S = R / LIN_SLICE;
   if ((size_t)S * d.n * J * sizeof(float) > ws_bytes) return false;
   float* part = reinterpret_cast<float*>(ws);
+  pack_clobbered(ws);
   const dim3 grid((unsigned)cdiv(J, 256), (unsigned)S);
   if (dgrad) {
     if (d.n <= 16) hipLaunchKernelGGL((linear_dgrad_part_kernel<16>), grid, dim3(256), 0, s, a, w, part, d.n, d.c, d.k);
@@ -1119,17 +1120,23 @@ static int pack_grid(size_t total) {
 // ---- weight packs of a whole network pass from ONE launch (cstp_pack_mode / cstp_pack_recorded / cstp_pack_replay, cstp_hip.h).
 // Every weight-pack launch of the convolution entry points goes through one of the three helpers below.  Per calling thread:
 // mode 0 = launch it (default); mode 1 = launch it AND append what was launched to the thread's record list; mode 2 = skip it --
-// the caller has replayed the recorded packs of this very call (same descriptor, same tile table, same weight and workspace
-// pointers) earlier on the stream.  A record IS the launch (kernel kind, pointers, integer arguments, block count), so whatever
+// the caller promises it has replayed the recorded packs of this very call (same descriptor, same tile table, same weight and
+// workspace pointers) earlier on the stream (unchecked: tests use it).  A record IS the launch (kernel kind, pointers, integer arguments, block count), so whatever
 // variant the dispatch picked is what gets replayed.
 static thread_local int tl_pack_mode = 0;
 static thread_local std::vector<cstp_pack_rec> tl_pack_recs;
-// ... and, without any per-call mode switch: workspaces the caller REGISTERED as holding replayed packs (cstp_pack_register) are
-// never packed into by the calls that receive them (process-wide, mutex-guarded; a relaxed counter keeps the common empty case
-// lock-free)
+// ... and, without any per-call mode switch: workspaces the caller REGISTERED as holding replayed packs (cstp_pack_register).  A
+// call that receives a registered workspace skips its pack only when the launch it is about to make EQUALS a record the caller
+// drained for that workspace (cstp_pack_recorded: kind, block count, pointers, integer arguments) -- what the replay wrote there
+// is then exactly what the call would write.  Any other launch (another kernel variant: operand alignment, an absmax cell or
+// not, a changed tile or arithmetic; another weight tensor) packs inside the call, and the workspace stops counting as replayed
+// until it is registered again: the call has overwritten the replayed pack.  Process-wide, mutex-guarded; a relaxed counter
+// keeps the common empty case lock-free.
 static std::mutex g_prepacked_mu;
 static std::unordered_set<const void*> g_prepacked;
+static std::unordered_map<const void*, std::vector<cstp_pack_rec>> g_drained;     // dst -> the records last drained for it
 static std::atomic<int> g_prepacked_n{0};
+// the workspace holds a replayed pack (mode 2, or registered and not overwritten since): the pack-free path of a call
 bool pack_skip(const void* dst) {
   if (tl_pack_mode == 2) return true;
   if (tl_pack_mode == 1 || g_prepacked_n.load(std::memory_order_relaxed) == 0) return false;
@@ -1137,51 +1144,73 @@ bool pack_skip(const void* dst) {
   return g_prepacked.count(dst) != 0;
 }
 
-void pack_record_b16(const float* w, void* dst, int nblocks, int kout, int cin, int ntaps, int Mp, int Kw, int dgrad, int ip) {
-  if (tl_pack_mode != 1) return;
+static void unregister_locked(std::unordered_set<const void*>::iterator it) {
+  g_prepacked.erase(it);
+  g_prepacked_n.store((int)g_prepacked.size(), std::memory_order_relaxed);
+}
+
+// something other than a recorded pack is written into ws (a bf16-triple pack, the linear path's partial sums)
+void pack_clobbered(const void* ws) {
+  if (g_prepacked_n.load(std::memory_order_relaxed) == 0) return;
+  std::lock_guard<std::mutex> lk(g_prepacked_mu);
+  auto it = g_prepacked.find(ws);
+  if (it != g_prepacked.end()) unregister_locked(it);
+}
+
+// every pack site: true = skip the launch r (the caller replayed it into r.dst); mode 1 appends it to the record list
+static bool pack_site(const cstp_pack_rec& r) {
+  if (tl_pack_mode == 2) return true;
+  if (tl_pack_mode == 1) {
+    tl_pack_recs.push_back(r);
+    return false;
+  }
+  if (g_prepacked_n.load(std::memory_order_relaxed) == 0) return false;
+  std::lock_guard<std::mutex> lk(g_prepacked_mu);
+  auto it = g_prepacked.find(r.dst);
+  if (it == g_prepacked.end()) return false;
+  auto d = g_drained.find(r.dst);
+  if (d != g_drained.end())
+    for (const cstp_pack_rec& q : d->second)
+      if (memcmp(&q, &r, sizeof(r)) == 0) return true;       // (records are zero-initialised: no padding, unused a[] are 0)
+  unregister_locked(it);
+  return false;
+}
+
+bool pack_site_b16(const float* w, void* dst, int nblocks, int kout, int cin, int ntaps, int Mp, int Kw, int dgrad, int ip) {
   cstp_pack_rec r{};
   r.kind = 4; r.nblocks = nblocks; r.w = w; r.dst = dst; r.inv_a = nullptr; r.cells = nullptr;
   const int a[7] = {kout, cin, ntaps, Mp, Kw, dgrad, ip};
   memcpy(r.a, a, sizeof(a));
-  tl_pack_recs.push_back(r);
+  return pack_site(r);
 }
 
 static void pack_site_split2(hipStream_t s, const float* w, unsigned* wps, float* inv_a, unsigned* cells, int ncells, int kout,
                              int cin, int ntaps, int Cp, int Mp, int ngroups, int dgrad) {
-  if (pack_skip(wps)) return;
-  if (tl_pack_mode == 1) {
-    cstp_pack_rec r{};
-    r.kind = 1; r.nblocks = Mp; r.w = w; r.dst = wps; r.inv_a = inv_a; r.cells = cells;
-    const int a[8] = {ncells, kout, cin, ntaps, Cp, Mp, ngroups, dgrad};
-    memcpy(r.a, a, sizeof(a));
-    tl_pack_recs.push_back(r);
-  }
+  cstp_pack_rec r{};
+  r.kind = 1; r.nblocks = Mp; r.w = w; r.dst = wps; r.inv_a = inv_a; r.cells = cells;
+  const int a[8] = {ncells, kout, cin, ntaps, Cp, Mp, ngroups, dgrad};
+  memcpy(r.a, a, sizeof(a));
+  if (pack_site(r)) return;
   hipLaunchKernelGGL(pack_weights_split2_kernel, dim3(Mp), dim3(256), 0, s, w, wps, inv_a, cells, ncells, kout, cin, ntaps, Cp, Mp,
                      ngroups, dgrad);
 }
 static void pack_site_patch(hipStream_t s, const float* w, uint4* wpk, float* inv_a, unsigned* cells, int ncells, int kout, int cin,
                             int ncb, int rows_per_blk, int nblk_rows, int dgrad, int nt) {
-  if (pack_skip(wpk)) return;
-  if (tl_pack_mode == 1) {
-    cstp_pack_rec r{};
-    r.kind = 2; r.nblocks = nblk_rows; r.w = w; r.dst = wpk; r.inv_a = inv_a; r.cells = cells;
-    const int a[7] = {ncells, kout, cin, ncb, rows_per_blk, dgrad, nt};
-    memcpy(r.a, a, sizeof(a));
-    tl_pack_recs.push_back(r);
-  }
+  cstp_pack_rec r{};
+  r.kind = 2; r.nblocks = nblk_rows; r.w = w; r.dst = wpk; r.inv_a = inv_a; r.cells = cells;
+  const int a[7] = {ncells, kout, cin, ncb, rows_per_blk, dgrad, nt};
+  memcpy(r.a, a, sizeof(a));
+  if (pack_site(r)) return;
   hipLaunchKernelGGL(pack_weights_patch_kernel, dim3(nblk_rows), dim3(256), 0, s, w, wpk, inv_a, cells, ncells, kout, cin, ncb,
                      rows_per_blk, dgrad, nt);
 }
 static void pack_site_native(hipStream_t s, const float* w, float* wp, int kout, int cin, int ntaps, int Cp, int Mp, int Kp, int dgrad) {
-  if (pack_skip(wp)) return;
   const int nb = pack_grid((size_t)Kp * Mp);
-  if (tl_pack_mode == 1) {
-    cstp_pack_rec r{};
-    r.kind = 3; r.nblocks = nb; r.w = w; r.dst = wp; r.inv_a = nullptr; r.cells = nullptr;
-    const int a[7] = {kout, cin, ntaps, Cp, Mp, Kp, dgrad};
-    memcpy(r.a, a, sizeof(a));
-    tl_pack_recs.push_back(r);
-  }
+  cstp_pack_rec r{};
+  r.kind = 3; r.nblocks = nb; r.w = w; r.dst = wp; r.inv_a = nullptr; r.cells = nullptr;
+  const int a[7] = {kout, cin, ntaps, Cp, Mp, Kp, dgrad};
+  memcpy(r.a, a, sizeof(a));
+  if (pack_site(r)) return;
   hipLaunchKernelGGL(pack_weights_kernel, dim3(nb), dim3(256), 0, s, w, wp, kout, cin, ntaps, Cp, Mp, Kp, dgrad);
 }
 
@@ -1247,6 +1276,7 @@ static void run_k1s(const Tile& tl, dim3 grid, hipStream_t s, const Geom& g, con
                     void* ws, size_t main_bytes, const uint32_t* src_absmax, const InAffine* ia = nullptr) {
   if (split_planes() == 3) {
     const size_t tot = (size_t)Kp * g.Mp;
+    pack_clobbered(ws);                               // (not recorded: packs inside the call in every mode)
     hipLaunchKernelGGL(pack_weights_split_kernel, dim3(pack_grid(tot / 2)), dim3(256), 0, s, w,
                        reinterpret_cast<unsigned short*>(ws), d.k, d.c, ntaps, g.Cp, g.Mp, Kp / 16, DGRAD ? 1 : 0);
     launch_k1s_np<DGRAD, 3>(tl, grid, s, g, reinterpret_cast<const uint4*>(ws), src, bias, out, ntx, ntm, nullptr, nullptr);
@@ -1772,8 +1802,16 @@ extern "C" int cstp_pack_mode(int32_t mode) {
 extern "C" int32_t cstp_pack_recorded(cstp_pack_rec* out, int32_t cap) {
   const int32_t n = (int32_t)tl_pack_recs.size();
   if (out != nullptr) {
-    for (int32_t i = 0; i < n && i < cap; ++i) out[i] = tl_pack_recs[i];
+    // the records handed out become the ones a registered workspace is checked against (pack_site): each drain replaces what
+    // an earlier one left for the same workspaces
+    std::unordered_map<const void*, std::vector<cstp_pack_rec>> fresh;
+    for (int32_t i = 0; i < n && i < cap; ++i) {
+      out[i] = tl_pack_recs[i];
+      fresh[out[i].dst].push_back(out[i]);
+    }
     tl_pack_recs.clear();
+    std::lock_guard<std::mutex> lk(g_prepacked_mu);
+    for (auto& kv : fresh) g_drained[kv.first] = std::move(kv.second);
   }
   return n;
 }
@@ -1781,7 +1819,10 @@ extern "C" int32_t cstp_pack_recorded(cstp_pack_rec* out, int32_t cap) {
 extern "C" int cstp_pack_register(const void* const* workspaces, int32_t n, int32_t on) {
   CSTP_REQUIRE(n >= 0 && (n == 0 || workspaces != nullptr), "bad argument");
   std::lock_guard<std::mutex> lk(g_prepacked_mu);
-  if (n == 0 && !on) g_prepacked.clear();
+  if (n == 0 && !on) {
+    g_prepacked.clear();
+    g_drained.clear();
+  }
   for (int32_t i = 0; i < n; ++i) {
     if (on) g_prepacked.insert(workspaces[i]); else g_prepacked.erase(workspaces[i]);
   }

@@ -31,7 +31,9 @@ __device__ __forceinline__ void pack_w_b16_body(const float* __restrict__ w, uns
 
 // the pack-plan hooks of igemm.hip (cstp_pack_mode / cstp_pack_register): true = the caller has replayed this workspace's pack
 bool pack_skip(const void* dst);
-// mode 1: append the launch about to be made to the calling thread's record list
-void pack_record_b16(const float* w, void* dst, int nblocks, int kout, int cin, int ntaps, int Mp, int Kw, int dgrad, int ip);
+// the bf16 pack site: true = skip this launch (it equals the record replayed into dst); mode 1 appends it to the record list
+bool pack_site_b16(const float* w, void* dst, int nblocks, int kout, int cin, int ntaps, int Mp, int Kw, int dgrad, int ip);
+// something other than a recorded pack is about to be written into ws: it no longer holds a replayed pack
+void pack_clobbered(const void* ws);
 
 }  // namespace cstp

@@ -76,7 +76,11 @@ class PackPlan:
     launches of every call (state "record"); from then on ``replay("online")`` at the top of a step and ``replay("target")``
     right behind the EMA run all recorded packs of that group from one launch each, and the calls skip theirs.  Outside an
     armed step (validation, fine-tuning, tests that call the model directly) nothing changes: calls pack for themselves.
-    A call whose (weight, tag, descriptor) was not recorded packs for itself too."""
+    A call whose key was not recorded packs for itself too, on a workspace of its own.  The key holds what picks the kernel
+    variant -- and with it the pack -- as far as the host sees it: the weight tensor, the direction, the input shape, whether
+    the call's activation operands are 16-byte aligned and whether it passes an absmax cell.  The library checks the rest: a
+    call on a registered workspace skips its pack only if that pack equals the recorded one, and otherwise packs for itself
+    (a tile or arithmetic changed behind the plan's back costs speed, never correctness)."""
 
     def __init__(self, target_range=None):
         self.state = "off"            # "off" | "record" | "replay"
@@ -88,8 +92,9 @@ class PackPlan:
         self.stats = {"replays": 0, "skipped_calls": 0, "recorded_calls": 0}
 
     @staticmethod
-    def key(w_param, tag, x_shape):
-        return (w_param.data_ptr(), tag, tuple(x_shape))      # (a weight tensor fixes kernel size, stride and padding)
+    def key(w_param, tag, x_shape, facts=()):
+        # (a weight tensor fixes kernel size, stride and padding; facts: _dispatch_facts of the call's operands)
+        return (w_param.data_ptr(), tag, tuple(x_shape)) + tuple(facts)
 
     def workspace(self, key, device, nbytes):
         ws = self.ws.get(key)
@@ -191,15 +196,23 @@ class PackPlan:
 pack_plan: Optional[PackPlan] = None          # set by the training step that owns the model (train.PretrainStep)
 
 
-def _packed_call(w_param, tag, x_shape, device, nbytes, fn):
+def _dispatch_facts(operands, absmax):
+    """What the library's kernel choice reads from a call's operands besides the descriptor and the tile table: the patch
+    kernels need 16-byte aligned activations (igemm.hip: a misaligned call takes the f16-pair gather kernel), and a fused input
+    transform needs the operand's absmax cell (else a native tile)."""
+    return (all(t.data_ptr() % 16 == 0 for t in operands), absmax is not None)
+
+
+def _packed_call(w_param, tag, x_shape, device, nbytes, fn, facts=()):
     """``fn(ws)`` = one C-ABI convolution call that packs ``w_param`` into its workspace: through the pack plan when a
-    training step has armed one (persistent workspace, recorded / skipped pack), else on the shared scratch arena."""
+    training step has armed one (persistent workspace, recorded / skipped pack), else on the shared scratch arena.
+    ``facts``: _dispatch_facts of the call (part of the plan's key)."""
     plan = pack_plan
     if plan is None or not plan.armed or plan.state == "off" or w_param is None:
         ws = _workspace(device, nbytes)
         fn(ws)
         return
-    key = PackPlan.key(w_param, tag, x_shape)
+    key = PackPlan.key(w_param, tag, x_shape, facts)
     ws = plan.workspace(key, device, nbytes)
     if plan.state == "record":
         plan.call(key, lambda: fn(ws))
@@ -597,7 +610,8 @@ class _Conv3d(torch.autograd.Function):
                                                  y.data_ptr(), ws.data_ptr(), ws.numel(), _ptr(xam)), "cstp_conv3d_forward")
 
         with _span("conv3d_forward", lambda: _desc_key(desc)):
-            _packed_call(w_in if w.data_ptr() == w_in.data_ptr() else None, "f", x.shape, x.device, nbytes, run)
+            _packed_call(w_in if w.data_ptr() == w_in.data_ptr() else None, "f", x.shape, x.device, nbytes, run,
+                         _dispatch_facts((x, y), xam))
         ctx.save_for_backward(x, w)
         ctx.w_param = w_in           # the parameter object itself (save_for_backward hands back a new tensor object)
         ctx.grad_join = grad_join
@@ -653,7 +667,8 @@ class _Conv3d(torch.autograd.Function):
                     _packed_call(ctx.w_param if w.data_ptr() == ctx.w_param.data_ptr() else None, "d", x.shape, x.device, nbytes,
                                  lambda ws: check(lib.cstp_conv3d_backward_data_acc(
                                      _stream(), ctypes.byref(desc), dy.data_ptr(), w.data_ptr(), dst.data_ptr(), ws.data_ptr(),
-                                     ws.numel(), _ptr(dyam), 1 if acc else 0), "cstp_conv3d_backward_data"))
+                                     ws.numel(), _ptr(dyam), 1 if acc else 0), "cstp_conv3d_backward_data"),
+                                 _dispatch_facts((dy, dst), dyam))
                 return dst
             join = ctx.grad_join
             if join is None:
@@ -922,7 +937,7 @@ class _BNReluConv3d(torch.autograd.Function):
         with _span("conv3d_forward", lambda: _desc_key(desc)):
             # ("fa": a forward that carries the in_affine may run another kernel variant -- another pack -- than the plain one)
             _packed_call(w_in if w.data_ptr() == w_in.data_ptr() else None, "fa", x.shape, x.device,
-                         lib.cstp_conv3d_workspace_bytes(ctypes.byref(desc)), run)
+                         lib.cstp_conv3d_workspace_bytes(ctypes.byref(desc)), run, _dispatch_facts((x, y), zam))
         ctx.save_for_backward(x, gamma, mean, invstd, ss, w)
         ctx.desc, ctx.groups, ctx.relu, ctx.z_absmax = desc, groups, relu, zam
         ctx.params = (g_in, b_in, w_in)      # the parameter objects themselves (their .grad may be an arena slice)
@@ -979,7 +994,8 @@ class _BNReluConv3d(torch.autograd.Function):
                              lib.cstp_conv3d_workspace_bytes(ctypes.byref(desc)),
                              lambda wsd: check(lib.cstp_conv3d_backward_data_acc(
                                  _stream(), ctypes.byref(desc), dy.data_ptr(), w.data_ptr(), dz.data_ptr(), wsd.data_ptr(),
-                                 wsd.numel(), _ptr(dyam), 0), "cstp_conv3d_backward_data"))
+                                 wsd.numel(), _ptr(dyam), 0), "cstp_conv3d_backward_data"),
+                             _dispatch_facts((dy, dz), dyam))
             dx = torch.empty_like(x)
             direct = ctx.needs_input_grad[1] and ctx.needs_input_grad[2] and _direct(pg) and _direct(pb)
             dgamma = pg.grad if direct else torch.empty_like(gamma)
@@ -1127,7 +1143,8 @@ class _Conv3dB16(torch.autograd.Function):
         with _span("conv3d_forward", lambda: ("bf16",) + _desc_key(desc)):
             _packed_call(w_in if w.data_ptr() == w_in.data_ptr() else None, "f", x.shape, x.device, nbytes,
                          lambda ws: check(lib.cstp_b16_conv3d_forward(_stream(), ctypes.byref(desc), x.data_ptr(), w.data_ptr(), y.data_ptr(),
-                                                                      ws.data_ptr(), ws.numel()), "cstp_b16_conv3d_forward"))
+                                                                      ws.data_ptr(), ws.numel()), "cstp_b16_conv3d_forward"),
+                         _dispatch_facts((x, y), None))
         ctx.save_for_backward(x, w)
         ctx.w_param = w_in
         ctx.desc = desc
@@ -1170,7 +1187,8 @@ class _Conv3dB16(torch.autograd.Function):
                     _packed_call(ctx.w_param if w.data_ptr() == ctx.w_param.data_ptr() else None, "d", x.shape, x.device, nbytes,
                                  lambda ws: check(lib.cstp_b16_conv3d_backward_data_acc(
                                      _stream(), ctypes.byref(desc), dy.data_ptr(), w.data_ptr(), dst.data_ptr(), ws.data_ptr(), ws.numel(),
-                                     1 if acc else 0), "cstp_b16_conv3d_backward_data"))
+                                     1 if acc else 0), "cstp_b16_conv3d_backward_data"),
+                                 _dispatch_facts((dy, dst), None))
                 return dst
             join = ctx.grad_join
             if join is None:

@@ -25,8 +25,8 @@
  *         table's key;
  *       * the deterministic-mode switch cstp_set_deterministic (atomic; ordered slabs instead of float atomics in the weight
  *         gradients), likewise process-wide;
- *       * the per-thread pack mode and record list (cstp_pack_mode) and the process-wide set of registered workspaces
- *         (cstp_pack_register; mutex-guarded);
+ *       * the per-thread pack mode and record list (cstp_pack_mode), the process-wide set of registered workspaces
+ *         (cstp_pack_register) and the records last drained for each (cstp_pack_recorded; both mutex-guarded);
  *       * environment knobs read once: CSTP_GEMM, CSTP_DETERMINISTIC, CSTP_PERSIST_CUS, CSTP_K1P_QUAD, CSTP_K1W, CSTP_LINEAR,
  *         CSTP_BN_SMALL, CSTP_TILE / CSTP_WTILE (developer overrides).
  *     A caller that wants two arithmetics side by side in one process must serialise the switch with its launches
@@ -166,8 +166,8 @@ int32_t cstp_gemm_get_split_terms(void);
  * bf16-storage path's operand rows; pointers,
  * integer arguments, blocks of 256 threads), so the replay does exactly what the call would have done -- provided descriptor,
  * tile table, weight pointer and workspace pointer are those of the recorded call.  first_block_dev[i] = sum of nblocks of the
- * records before i; total_blocks = the sum over all.  The mode is per calling THREAD (0 = default).  bf16-triple packs are not
- * recorded (they keep packing inside the call in every mode). */
+ * records before i; total_blocks = the sum over all.  The mode is per calling THREAD (0 = default).  Mode 2 is an unchecked
+ * promise (for tests).  bf16-triple packs are not recorded (they keep packing inside the call in every mode). */
 typedef struct cstp_pack_rec {
   int32_t kind, nblocks;
   const float* w;
@@ -180,7 +180,13 @@ int cstp_pack_mode(int32_t mode);
 int32_t cstp_pack_recorded(cstp_pack_rec* out, int32_t cap);
 int cstp_pack_replay(void* stream, const cstp_pack_rec* recs_dev, const int32_t* first_block_dev, int32_t n, int32_t total_blocks);
 /* ... or, instead of mode 2 around every call: REGISTER the workspaces (the records' dst pointers) whose packs the caller replays --
- * a call that receives a registered workspace skips its pack (on = 0: unregister; n = 0 with on = 0: forget all).  Process-wide. */
+ * a call that receives a registered workspace skips its pack ONLY IF the pack it would launch equals a record that
+ * cstp_pack_recorded handed out for that workspace (kind, nblocks, w, inv_a, cells, a[]; each drain replaces the records an
+ * earlier one left for the same workspaces).  Any other pack -- another kernel variant (operand alignment, an absmax cell or
+ * not, a tile or arithmetic changed since the recording), another weight tensor, a workspace without a record -- runs inside
+ * the call, and that workspace stops counting as registered until it is registered again; so does a workspace that a call
+ * uses for something other than a recorded pack (a bf16-triple pack, a linear layer's partial sums).  on = 0: unregister;
+ * n = 0 with on = 0: forget all registrations and records.  Process-wide. */
 int cstp_pack_register(const void* const* workspaces, int32_t n, int32_t on);
 
 /* Which kernel variant the next forward (mode 0) / backward_data (mode 1) / backward_weight (mode 2) call with this
