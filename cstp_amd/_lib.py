@@ -32,6 +32,12 @@ class PackRec(ctypes.Structure):
                 ("cells", c_void_p), ("a", c_int32 * 10)]
 
 
+class GateBranch(ctypes.Structure):
+    """struct cstp_gate_branch: one branch of a fused S3D-G self-gating + concat call (cstp_gate_concat_*)."""
+    _fields_ = [("x", c_void_p), ("w", c_void_p), ("b", c_void_p), ("dx", c_void_p), ("dw", c_void_p), ("db", c_void_p),
+                ("c", c_int32), ("reserved", c_int32)]
+
+
 class CstpError(RuntimeError):
     pass
 
@@ -140,6 +146,11 @@ SIGNATURES = {
                                               POINTER(c_int32), POINTER(c_int32)]),
     "cstp_b16_avgpool_forward": (c_int32, [_P, _P, _P, c_int32, c_int32]),
     "cstp_b16_avgpool_backward": (c_int32, [_P, _P, _P, c_int32, c_int32]),
+    # S3D-G self-gating + inception concat (csrc/gate.hip)
+    "cstp_gate_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "cstp_gate_concat_forward": (c_int32, [_P, POINTER(GateBranch), c_int32, c_int32, c_int32, _P, _P, _P, _P]),
+    "cstp_gate_concat_backward": (c_int32, [_P, POINTER(GateBranch), c_int32, c_int32, c_int32, _P, _P, _P, _P, c_size_t,
+                                            c_int32]),
 }
 
 _lib = None

@@ -793,6 +793,9 @@ static bool twpatch_geom_ok(const cstp_conv_desc& d) {
     return false;
   if (native_only() || split_planes() != 2 || d.c < 16 || d.k < 16) return false;
   if ((d.h * d.w) % 16 != 0 || d.d > 255) return false;      // chunks of 32 positions, or of 16 (28 x 28 frames)
+  // one chunk per frame serves one clip only: the item -> (clip, chunk) division multiplies by ceil(2^32 / chunks), which does not
+  // fit in 32 bits for ONE chunk, so every item would land on clip 0 (S3D-G's Mixed_3b/3c on 4 x 4 frames, 8 x 32 x 32 clips)
+  if (d.h * d.w / ((d.h * d.w) % 32 == 0 ? 32 : 16) < 2 && d.n > 1) return false;
   return (long)d.n * (d.h * d.w / 16) * (d.d + 1) < (1l << 26);
 }
 static inline bool split_mt_ok(int mt) { return mt == 2 || mt == 3 || mt == 4 || mt == 5 || mt == 6 || mt == 8 || mt == 9; }

@@ -23,6 +23,8 @@ from torch import nn
 
 from .r21d_byol import R21DBYOL, get_fine_tuning_parameters, layer_sizes_for_depth
 from .r3d_byol import R3DBYOL
+from .s3dg_byol import S3DGBYOL
+from .s3dg_byol import get_fine_tuning_parameters as s3dg_fine_tuning_parameters
 
 PRETRAIN_TASKS = ("r_byol", "loss_com")
 FINETUNE_TASKS = ("ft_fc", "ft_all", "scratch", "test", "resume")
@@ -65,8 +67,8 @@ def _load_checkpoint(path, device):
 
 
 def generate_model(opts):
-    if opts.model_name not in ("r21d_byol", "r3d_byol"):
-        raise ValueError("Please check the input backbone! (cstp_amd provides model_name=r21d_byol | r3d_byol, got %r)"
+    if opts.model_name not in ("r21d_byol", "r3d_byol", "s3d_byol"):
+        raise ValueError("Please check the input backbone! (cstp_amd provides model_name=r21d_byol | r3d_byol | s3d_byol, got %r)"
                          % (opts.model_name,))
     if opts.task not in PRETRAIN_TASKS + FINETUNE_TASKS:
         raise ValueError("task %r: r21d_byol serves %s" % (opts.task, PRETRAIN_TASKS + FINETUNE_TASKS))
@@ -77,6 +79,10 @@ def generate_model(opts):
             model = R3DBYOL(pretrain=True, opts=opts)
         else:
             model = R3DBYOL(pretrain=False, cls_bn=True, opts=opts)
+    elif opts.model_name == "s3d_byol":      # models/model.py:54-59: S3DGBYOL(pretrain=..., gating=True, slow=False, ...)
+        act = getattr(opts, "act_dtype", "fp32") or "fp32"
+        model = S3DGBYOL(pretrain=opts.task in PRETRAIN_TASKS, gating=True, slow=False, num_classes=opts.n_classes,
+                         act_dtype=act)
     else:
         act = getattr(opts, "act_dtype", "fp32") or "fp32"
         layer_sizes = layer_sizes_for_depth(opts.model_depth)
@@ -101,7 +107,8 @@ def generate_model(opts):
     frozen_plan = None
     if opts.task in ("ft_fc", "ft_all"):
         if opts.ft_begin_index != 0:    # substring match on names: the later ``module.`` prefix cannot change it
-            frozen_plan = get_fine_tuning_parameters(inner, opts.ft_begin_index)
+            plan = s3dg_fine_tuning_parameters if opts.model_name == "s3d_byol" else get_fine_tuning_parameters
+            frozen_plan = plan(inner, opts.ft_begin_index)
     if getattr(opts, "distributed", False):
         # gradient all-reduce (mean) on RCCL over xGMI.  DDP's default broadcast_buffers=True is kept, but the training
         # steps run forward/backward under no_sync(), which stops DDP's own buffer broadcast after the first forward: they

@@ -1109,6 +1109,98 @@ def global_avg_pool(x):
 
 
 # ----------------------------------------------------------------------------------------------
+# S3D-G self-gating fused with the inception concat (csrc/gate.hip)
+# ----------------------------------------------------------------------------------------------
+class _GateConcat(torch.autograd.Function):
+    """y = cat_i(sigmoid(fc_i(mean_s x_i)) * x_i) over the branches of one SepInception block (s3dg.py:100-110, :150-163):
+    two launches forward, three backward, for all branches together."""
+    _last_cell = None
+
+    @staticmethod
+    def forward(ctx, nb, save, *args):
+        lib = _lib.load()
+        xs = [_req(x, "gate_concat branch") for x in args[:nb]]
+        ws = [_req(w, "gate_concat weight") for w in args[nb:2 * nb]]
+        bs = [_req(b, "gate_concat bias") for b in args[2 * nb:3 * nb]]
+        n, spatial = xs[0].shape[0], tuple(xs[0].shape[2:])
+        for x, w, b in zip(xs, ws, bs):
+            c = x.shape[1]
+            if x.dim() != 5 or x.shape[0] != n or tuple(x.shape[2:]) != spatial:
+                raise _lib.CstpError("gate_concat branches must be [N, C_i, D, H, W] with one N, D, H, W; got %s"
+                                     % ([tuple(t.shape) for t in xs],))
+            if tuple(w.shape) != (c, c) or tuple(b.shape) != (c,):
+                raise _lib.CstpError("gate_concat branch of %d channels needs a [%d, %d] weight and a [%d] bias, got %s, %s"
+                                     % (c, c, c, c, tuple(w.shape), tuple(b.shape)))
+        cs = [x.shape[1] for x in xs]
+        ctot = sum(cs)
+        s = xs[0].numel() // (n * cs[0])
+        dev = xs[0].device
+        y = torch.empty((n, ctot) + spatial, dtype=torch.float32, device=dev)
+        m = torch.empty(n * ctot, dtype=torch.float32, device=dev)
+        g = torch.empty(n * ctot, dtype=torch.float32, device=dev) if save else None
+        cell = _new_cell(y)
+        br = (_lib.GateBranch * nb)(*[_lib.GateBranch(x.data_ptr(), w.data_ptr(), b.data_ptr(), None, None, None, c, 0)
+                                     for x, w, b, c in zip(xs, ws, bs, cs)])
+        with _span("gate_forward", (n, s, tuple(cs))):
+            check(lib.cstp_gate_concat_forward(_stream(), br, nb, n, s, y.data_ptr(), m.data_ptr(), _ptr(g), _ptr(cell)),
+                  "cstp_gate_concat_forward")
+        _GateConcat._last_cell = cell
+        if save:
+            ctx.save_for_backward(*xs, *ws, m, g)
+            ctx.params = args[nb:3 * nb]       # the parameter objects themselves (.grad may be an arena slice)
+        ctx.nb, ctx.save, ctx.geom = nb, save, (n, s, tuple(cs))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        if not ctx.save:
+            raise RuntimeError("gate_concat: forward ran without saving its gates (no gradient was required then)")
+        lib = _lib.load()
+        nb = ctx.nb
+        saved = ctx.saved_tensors
+        xs, ws, m, g = saved[:nb], saved[nb:2 * nb], saved[2 * nb], saved[2 * nb + 1]
+        n, s, cs = ctx.geom
+        dy = _req(dy, "gate_concat grad_output")
+        dxs = [torch.empty_like(x) for x in xs]
+        # gradients of leaf parameters whose .grad is a live slice of the flat arena are added there by the kernel (as the BN ops do)
+        direct = all(ctx.needs_input_grad[2 + nb:2 + 3 * nb]) and all(_direct(p) for p in ctx.params)
+        dws = [p.grad for p in ctx.params[:nb]] if direct else [torch.empty_like(w) for w in ws]
+        dbs = [p.grad for p in ctx.params[nb:]] if direct else [torch.empty(c, dtype=torch.float32, device=dy.device) for c in cs]
+        br = (_lib.GateBranch * nb)(*[_lib.GateBranch(x.data_ptr(), w.data_ptr(), b.data_ptr(), dx.data_ptr(), dw.data_ptr(),
+                                                      db.data_ptr(), c, 0)
+                                     for x, w, b, dx, dw, db, c in zip(xs, ws, ctx.params[nb:], dxs, dws, dbs, cs)])
+        nbytes = lib.cstp_gate_workspace_bytes(n, sum(cs))
+        wsp = _workspace(dy.device, nbytes)
+        with _span("gate_backward", (n, s, tuple(cs))):
+            check(lib.cstp_gate_concat_backward(_stream(), br, nb, n, s, dy.data_ptr(), m.data_ptr(), g.data_ptr(), wsp.data_ptr(),
+                                                wsp.numel(), 1 if direct else 0), "cstp_gate_concat_backward")
+        if direct:
+            return (None, None, *dxs) + (None,) * (2 * nb)
+        return (None, None, *dxs, *dws, *dbs)
+
+
+def gate_concat(branches, gates):
+    """S3D-G SepInception tail (fp32): ``torch.cat([sigmoid(fc(x.mean([2, 3, 4])))[..., None, None, None] * x for x, fc in
+    zip(branches, gates)], 1)`` with ``gates`` the (weight [c, c], bias [c]) pairs of the branches' SelfGating.fc.  The result is
+    tagged with its max |y| cell for the 1x1x1 convolutions that consume it.  The gates are saved for backward only when a
+    gradient is required."""
+    branches, gates = list(branches), list(gates)
+    if not 1 <= len(branches) <= 4 or len(gates) != len(branches):
+        raise _lib.CstpError("gate_concat takes 1..4 branches with one (weight, bias) pair each, got %d and %d"
+                             % (len(branches), len(gates)))
+    ws = [w for w, _ in gates]
+    bs = [b for _, b in gates]
+    for t in branches + ws + bs:
+        if t.dtype == torch.bfloat16:
+            raise _lib.CstpError("gate_concat is fp32 only (S3D-G has no bf16-storage path)")
+    save = torch.is_grad_enabled() and any(t.requires_grad for t in branches + ws + bs)
+    y = _GateConcat.apply(len(branches), save, *branches, *ws, *bs)
+    _tag_absmax(y, _GateConcat._last_cell)
+    _GateConcat._last_cell = None
+    return y
+
+
+# ----------------------------------------------------------------------------------------------
 # the bf16-STORAGE path (csrc/b16.hip; BASELINE configs[4]), selected by the dtype of the activation tensor:
 # 5-D activations and their gradients bf16, parameters / their gradients / statistics fp32 (cstp_hip.h "bf16-STORAGE path")
 # ----------------------------------------------------------------------------------------------

@@ -450,6 +450,36 @@ int cstp_b16_maxpool3d_backward(void* stream, const uint16_t* dy, const int32_t*
 int cstp_b16_avgpool_forward(void* stream, const uint16_t* x, float* y, int32_t rows, int32_t s);
 int cstp_b16_avgpool_backward(void* stream, const float* dy, uint16_t* dx, int32_t rows, int32_t s);
 
+/* ---- S3D-G self-gating fused with the inception concat (csrc/gate.hip) -------------------------------------------------
+ * Replaces, per SepInception block (models/coclr/s3dg.py:100-110, :150-163), the four SelfGating calls
+ *   torch.mean(x_i, dim=[2,3,4]) -> fc_i (Linear c_i x c_i) -> torch.sigmoid -> weights[:, :, None, None, None] * x_i
+ * and the torch.cat((x0, x1, x2, x3), 1) that follows them.  Branch i: x_i [n][c_i][s] (the output of its last BN+ReLU),
+ * w_i [c_i][c_i], b_i [c_i]; it occupies channels [o_i, o_i + c_i) of y [n][C][s], C = sum c_i, o_i = c_0 + .. + c_{i-1}.
+ * m [n][C] receives the means, g [n][C] the gates.  Reductions run in a fixed order and no float atomics are used: two calls
+ * with the same inputs give bit-identical outputs. */
+typedef struct cstp_gate_branch {
+  const float* x;      /* [n][c][s] branch output */
+  const float* w;      /* [c][c] gating Linear weight (fc.weight) */
+  const float* b;      /* [c] gating Linear bias (fc.bias) */
+  float* dx;           /* backward: [n][c][s] */
+  float* dw;           /* backward: [c][c] */
+  float* db;           /* backward: [c] */
+  int32_t c;           /* channels of this branch */
+  int32_t reserved;    /* 0 */
+} cstp_gate_branch;
+#define CSTP_GATE_MAX_BRANCHES 4
+/* Forward, two launches: means, then gate + apply straight into the concat tensor y.  m is required (the apply launch
+ * reads it); g may be NULL (no gradient needed).  y_absmax (optional): max |y| as fp32 bits (see cstp_bn_forward_train_am). */
+int cstp_gate_concat_forward(void* stream, const cstp_gate_branch* branches, int32_t nbranch, int32_t n, int32_t s, float* y,
+                             float* m, float* g, uint32_t* y_absmax);
+size_t cstp_gate_workspace_bytes(int32_t n, int32_t ctot);
+/* Backward, three launches, given dy [n][C][s] of the whole concat tensor (read through each branch's channel offset):
+ *   t = sum_s dy * x,  d = t g (1 - g),  dw_i = sum_n d_i (x) m_i,  db_i = sum_n d_i,  dm_i[n][k] = sum_c w_i[c][k] d_i[n][c],
+ *   dx_i = g dy + dm_i / s.
+ * accumulate != 0: dw / db are ADDED to (a flat gradient arena), else written. */
+int cstp_gate_concat_backward(void* stream, const cstp_gate_branch* branches, int32_t nbranch, int32_t n, int32_t s,
+                              const float* dy, const float* m, const float* g, void* ws, size_t ws_bytes, int32_t accumulate);
+
 #ifdef __cplusplus
 }
 #endif
