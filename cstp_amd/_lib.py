@@ -38,6 +38,13 @@ class GateBranch(ctypes.Structure):
                 ("c", c_int32), ("reserved", c_int32)]
 
 
+class BncBranch(ctypes.Structure):
+    """struct cstp_bnc_branch: one branch of a fused I3D BatchNorm + ReLU + concat call (cstp_bnrelu_concat_*)."""
+    _fields_ = [("x", c_void_p), ("gamma", c_void_p), ("beta", c_void_p), ("running_mean", c_void_p), ("running_var", c_void_p),
+                ("part", c_void_p), ("dx", c_void_p), ("dgamma", c_void_p), ("dbeta", c_void_p), ("dx_absmax", c_void_p),
+                ("c", c_int32), ("nsplit", c_int32)]
+
+
 class CstpError(RuntimeError):
     pass
 
@@ -151,6 +158,20 @@ SIGNATURES = {
     "cstp_gate_concat_forward": (c_int32, [_P, POINTER(GateBranch), c_int32, c_int32, c_int32, _P, _P, _P, _P]),
     "cstp_gate_concat_backward": (c_int32, [_P, POINTER(GateBranch), c_int32, c_int32, c_int32, _P, _P, _P, _P, c_size_t,
                                             c_int32]),
+    # I3D: SAME max-pool, windowed average pool, BatchNorm + ReLU into the inception concat (csrc/mixed.hip)
+    "cstp_maxpool3d_same_out": (c_int32, [c_int32, c_int32, c_int32]),
+    "cstp_maxpool3d_same_forward": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32),
+                                              POINTER(c_int32)]),
+    "cstp_maxpool3d_same_backward": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32),
+                                               POINTER(c_int32)]),
+    "cstp_avgpool3d_window_forward": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32)]),
+    "cstp_avgpool3d_window_backward": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, POINTER(c_int32)]),
+    "cstp_bnrelu_concat_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "cstp_bnrelu_concat_forward": (c_int32, [_P, POINTER(BncBranch), c_int32, c_int32, c_int32, c_int32, c_float, c_float, _P, _P,
+                                             _P, _P, _P, c_size_t, _P]),
+    "cstp_bnrelu_concat_eval": (c_int32, [_P, POINTER(BncBranch), c_int32, c_int32, c_int32, c_float, _P, _P, _P]),
+    "cstp_bnrelu_concat_backward": (c_int32, [_P, POINTER(BncBranch), c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P,
+                                              c_size_t, c_int32]),
 }
 
 _lib = None

@@ -22,6 +22,8 @@ import torch
 from torch import nn
 
 from .r21d_byol import R21DBYOL, get_fine_tuning_parameters, layer_sizes_for_depth
+from .i3d_byol import I3DBYOL
+from .i3d_byol import get_fine_tuning_parameters as i3d_fine_tuning_parameters
 from .r3d_byol import R3DBYOL
 from .s3dg_byol import S3DGBYOL
 from .s3dg_byol import get_fine_tuning_parameters as s3dg_fine_tuning_parameters
@@ -67,11 +69,19 @@ def _load_checkpoint(path, device):
 
 
 def generate_model(opts):
-    if opts.model_name not in ("r21d_byol", "r3d_byol", "s3d_byol"):
-        raise ValueError("Please check the input backbone! (cstp_amd provides model_name=r21d_byol | r3d_byol | s3d_byol, got %r)"
-                         % (opts.model_name,))
+    if opts.model_name not in ("r21d_byol", "r3d_byol", "s3d_byol", "i3d_byol"):
+        raise ValueError("Please check the input backbone! (cstp_amd provides model_name=r21d_byol | r3d_byol | s3d_byol | "
+                         "i3d_byol, got %r)" % (opts.model_name,))
     if opts.task not in PRETRAIN_TASKS + FINETUNE_TASKS:
         raise ValueError("task %r: r21d_byol serves %s" % (opts.task, PRETRAIN_TASKS + FINETUNE_TASKS))
+    if opts.model_name == "i3d_byol" and opts.task == "ft_fc":
+        # models/BE/i3d_byol.py:17-38 keeps parameters whose name contains 'layer<i>' or 'fc' trainable: I3D has none
+        raise ValueError("--task ft_fc with i3d_byol leaves nothing to train: the fine-tune plan matches parameter names "
+                         "containing 'layer<i>' or 'fc' and no I3D parameter has one (the classifier is "
+                         "online_net.conv3d_0c_1x1_custom.conv3d.weight); use --task ft_all")
+    if opts.model_name == "i3d_byol" and opts.task == "scratch":
+        raise ValueError("--task scratch with i3d_byol: the reference's factory builds no model for it (models/model.py:66-71) "
+                         "and I3DBYOL has no `classify` for o_type='scratch'; use --task ft_all without --pretrained_path weights")
     if not torch.cuda.is_available():
         raise RuntimeError("generate_model needs a HIP device: cstp_amd has no CPU execution path")
     if opts.model_name == "r3d_byol":        # models/model.py:65-70: R3DBYOL(pretrain=..., [cls_bn=True,] opts=opts)
@@ -79,6 +89,8 @@ def generate_model(opts):
             model = R3DBYOL(pretrain=True, opts=opts)
         else:
             model = R3DBYOL(pretrain=False, cls_bn=True, opts=opts)
+    elif opts.model_name == "i3d_byol":      # models/model.py:66-71: I3DBYOL(pretrain=..., opts=opts)
+        model = I3DBYOL(pretrain=opts.task in PRETRAIN_TASKS, opts=opts)
     elif opts.model_name == "s3d_byol":      # models/model.py:54-59: S3DGBYOL(pretrain=..., gating=True, slow=False, ...)
         act = getattr(opts, "act_dtype", "fp32") or "fp32"
         model = S3DGBYOL(pretrain=opts.task in PRETRAIN_TASKS, gating=True, slow=False, num_classes=opts.n_classes,
@@ -107,7 +119,8 @@ def generate_model(opts):
     frozen_plan = None
     if opts.task in ("ft_fc", "ft_all"):
         if opts.ft_begin_index != 0:    # substring match on names: the later ``module.`` prefix cannot change it
-            plan = s3dg_fine_tuning_parameters if opts.model_name == "s3d_byol" else get_fine_tuning_parameters
+            plan = {"s3d_byol": s3dg_fine_tuning_parameters, "i3d_byol": i3d_fine_tuning_parameters}.get(
+                opts.model_name, get_fine_tuning_parameters)
             frozen_plan = plan(inner, opts.ft_begin_index)
     if getattr(opts, "distributed", False):
         # gradient all-reduce (mean) on RCCL over xGMI.  DDP's default broadcast_buffers=True is kept, but the training

@@ -1201,6 +1201,249 @@ def gate_concat(branches, gates):
 
 
 # ----------------------------------------------------------------------------------------------
+# I3D (csrc/mixed.hip): TensorFlow-SAME max-pool, windowed average pool, BatchNorm + ReLU written into the inception concat
+# ----------------------------------------------------------------------------------------------
+def same_pool_geometry(n: int, k: int, s: int) -> Tuple[int, int, int]:
+    """(front padding, back padding, output length) of one dimension of MaxPool3dTFPadding (models/BE/i3d_byol.py:70-87,
+    :170-183): ``MaxPool3d(k, s, ceil_mode=True)`` over ``ConstantPad3d`` with ``pad = max(k - s, 0)`` split front ``pad // 2`` /
+    back the rest.  Output ``ceil((n + pad - k) / s) + 1``, one less when the last window would start at or beyond the padded
+    length (ATen's ceil-mode rule; the pooling's own padding is 0).  Pure host arithmetic, mirrored by cstp_maxpool3d_same_out."""
+    n, k, s = int(n), int(k), int(s)
+    if n < 1 or k < 1 or s < 1:
+        raise ValueError("same_pool_geometry needs positive n, kernel and stride, got %r" % ((n, k, s),))
+    pad = max(k - s, 0)
+    front = pad // 2
+    out = -((n + pad - k) // -s) + 1
+    if (out - 1) * s >= n + pad:
+        out -= 1
+    return front, pad - front, out
+
+
+class _MaxPool3dSame(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, kernel, stride, save):
+        lib = _lib.load()
+        x = _req(x, "max_pool3d_same input")
+        if x.dim() != 5:
+            raise _lib.CstpError("max_pool3d_same expects [N, C, D, H, W], got %s" % (tuple(x.shape),))
+        n, c, d, h, w = x.shape
+        osz = tuple(same_pool_geometry(sz, kernel[i], stride[i])[2] for i, sz in enumerate((d, h, w)))
+        y = torch.empty((n, c) + osz, dtype=torch.float32, device=x.device)
+        idx = torch.empty((n, c) + osz, dtype=torch.int32, device=x.device) if save else None
+        check(lib.cstp_maxpool3d_same_forward(_stream(), x.data_ptr(), y.data_ptr(), _ptr(idx), n * c, d, h, w,
+                                              (ctypes.c_int32 * 3)(*kernel), (ctypes.c_int32 * 3)(*stride)),
+              "cstp_maxpool3d_same_forward")
+        if save:
+            ctx.save_for_backward(idx)
+        ctx.geom = (tuple(x.shape), tuple(kernel), tuple(stride))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        (idx,) = ctx.saved_tensors
+        shape, kernel, stride = ctx.geom
+        dy = _req(dy, "max_pool3d_same grad_output")
+        dx = torch.empty(shape, dtype=torch.float32, device=dy.device)
+        n, c, d, h, w = shape
+        check(lib.cstp_maxpool3d_same_backward(_stream(), dy.data_ptr(), idx.data_ptr(), dx.data_ptr(), n * c, d, h, w,
+                                               (ctypes.c_int32 * 3)(*kernel), (ctypes.c_int32 * 3)(*stride)),
+              "cstp_maxpool3d_same_backward")
+        return dx, None, None, None
+
+
+def max_pool3d_same(x, kernel_size, stride):
+    """MaxPool3dTFPadding (i3d_byol.py:170-183): ``MaxPool3d(k, s, ceil_mode=True)(ConstantPad3d(get_padding_shape(k, s), 0)(x))``
+    in one kernel, without the padded copy: a padding position is a candidate of value 0 (and swallows the gradient when it
+    wins).  fp32 only."""
+    if x.dtype == torch.bfloat16:
+        raise _lib.CstpError("max_pool3d_same is fp32 only (I3D has no bf16-storage path)")
+    # the argmax is written only when a gradient can be asked for
+    return _MaxPool3dSame.apply(x, _triple(kernel_size), _triple(stride), torch.is_grad_enabled() and x.requires_grad)
+
+
+class _AvgPool3dWindow(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, kernel):
+        lib = _lib.load()
+        x = _req(x, "avg_pool3d_window input")
+        n, c, d, h, w = x.shape
+        y = torch.empty((n, c, d - kernel[0] + 1, h - kernel[1] + 1, w - kernel[2] + 1), dtype=torch.float32, device=x.device)
+        check(lib.cstp_avgpool3d_window_forward(_stream(), x.data_ptr(), y.data_ptr(), n * c, d, h, w,
+                                                (ctypes.c_int32 * 3)(*kernel)), "cstp_avgpool3d_window_forward")
+        ctx.geom = (tuple(x.shape), tuple(kernel))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        shape, kernel = ctx.geom
+        dy = _req(dy, "avg_pool3d_window grad_output")
+        dx = torch.empty(shape, dtype=torch.float32, device=dy.device)
+        n, c, d, h, w = shape
+        check(lib.cstp_avgpool3d_window_backward(_stream(), dy.data_ptr(), dx.data_ptr(), n * c, d, h, w,
+                                                 (ctypes.c_int32 * 3)(*kernel)), "cstp_avgpool3d_window_backward")
+        return dx, None
+
+
+def avg_pool3d_window(x, kernel_size):
+    """nn.AvgPool3d(kernel_size, stride 1) over valid windows (i3d_byol.py:297), [N, C, D, H, W] fp32.  A window that covers the
+    whole volume is the global average pool and goes to its kernel."""
+    kernel = _triple(kernel_size)
+    if x.dim() != 5:
+        raise _lib.CstpError("avg_pool3d_window expects [N, C, D, H, W], got %s" % (tuple(x.shape),))
+    if any(k < 1 or k > sz for k, sz in zip(kernel, x.shape[2:])):
+        raise _lib.CstpError("avg_pool3d_window: kernel %s does not fit the %s volume" % (kernel, tuple(x.shape[2:])))
+    if tuple(x.shape[2:]) == kernel:
+        return global_avg_pool(x).reshape(x.shape[0], x.shape[1], 1, 1, 1)
+    return _AvgPool3dWindow.apply(x, kernel)
+
+
+class _BNReluConcat(torch.autograd.Function):
+    """y = cat_i(relu(batch_norm_train(x_i))) over the branches of one I3D Mixed block (i3d_byol.py:214-220): two launches
+    forward (three when a branch brings no statistics), two backward, for all branches together.  Saved for backward, in this
+    order: the nb inputs, the nb weights, save_mean and save_invstd [groups * C], the (scale, shift) table."""
+    _last_cell = None
+    _pre_stats = None      # per branch: what the producing convolution left (bn_relu_concat sets it)
+
+    @staticmethod
+    def forward(ctx, nb, save, groups, eps, momentum, running, *args):
+        lib = _lib.load()
+        xs = [_req(x, "bn_relu_concat branch") for x in args[:nb]]
+        gammas = [_req(g, "bn_relu_concat weight") for g in args[nb:2 * nb]]
+        betas = [_req(b, "bn_relu_concat bias") for b in args[2 * nb:3 * nb]]
+        n, spatial = xs[0].shape[0], tuple(xs[0].shape[2:])
+        for x, g, b in zip(xs, gammas, betas):
+            if x.dim() != 5 or x.shape[0] != n or tuple(x.shape[2:]) != spatial:
+                raise _lib.CstpError("bn_relu_concat branches must be [N, C_i, D, H, W] with one N, D, H, W; got %s"
+                                     % ([tuple(t.shape) for t in xs],))
+            if tuple(g.shape) != (x.shape[1],) or tuple(b.shape) != (x.shape[1],):
+                raise _lib.CstpError("bn_relu_concat branch of %d channels needs [%d] weight and bias, got %s, %s"
+                                     % (x.shape[1], x.shape[1], tuple(g.shape), tuple(b.shape)))
+        if groups < 1 or n % groups != 0:
+            raise _lib.CstpError("batch of %d rows cannot be split into %d BN groups" % (n, groups))
+        cs = [x.shape[1] for x in xs]
+        ctot = sum(cs)
+        s = xs[0].numel() // (n * cs[0])
+        dev = xs[0].device
+        pre = _BNReluConcat._pre_stats or [None] * nb
+        _BNReluConcat._pre_stats = None
+        y = torch.empty((n, ctot) + spatial, dtype=torch.float32, device=dev)
+        mean = torch.empty(groups * ctot, dtype=torch.float32, device=dev)
+        invstd = torch.empty(groups * ctot, dtype=torch.float32, device=dev)
+        ss = torch.empty(groups * ctot * 2, dtype=torch.float32, device=dev)
+        cell = _new_cell(y)
+        wsp = _workspace(dev, lib.cstp_bnrelu_concat_workspace_bytes(ctot, groups))
+        br = (_lib.BncBranch * nb)(*[
+            _lib.BncBranch(x.data_ptr(), g.data_ptr(), b.data_ptr(), _ptr(rm), _ptr(rv), None if p is None else p[0].data_ptr(),
+                           None, None, None, None, c, 0 if p is None else p[1])
+            for x, g, b, (rm, rv), p, c in zip(xs, gammas, betas, running, pre, cs)])
+        with _span("bnc_forward", (n, s, groups, tuple(cs))):
+            check(lib.cstp_bnrelu_concat_forward(_stream(), br, nb, n, s, groups, eps, momentum, y.data_ptr(), mean.data_ptr(),
+                                                 invstd.data_ptr(), ss.data_ptr(), wsp.data_ptr(), wsp.numel(), _ptr(cell)),
+                  "cstp_bnrelu_concat_forward")
+        _BNReluConcat._last_cell = cell
+        if save:
+            ctx.save_for_backward(*xs, *gammas, mean, invstd, ss)
+            ctx.params = args[nb:3 * nb]       # the parameter objects themselves (.grad may be an arena slice)
+        ctx.nb, ctx.save, ctx.geom = nb, save, (n, s, groups, tuple(cs))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        if not ctx.save:
+            raise RuntimeError("bn_relu_concat: forward ran without saving its statistics (no gradient was required then)")
+        lib = _lib.load()
+        nb = ctx.nb
+        saved = ctx.saved_tensors
+        xs, gammas = saved[:nb], saved[nb:2 * nb]
+        mean, invstd, ss = saved[2 * nb:2 * nb + 3]
+        n, s, groups, cs = ctx.geom
+        dy = _req(dy, "bn_relu_concat grad_output")
+        dxs = [torch.empty_like(x) for x in xs]
+        # gradients of leaf parameters whose .grad is a live slice of the flat arena are added there by the kernel (as _BNAct does)
+        direct = all(ctx.needs_input_grad[6 + nb:6 + 3 * nb]) and all(_direct(p) for p in ctx.params)
+        dgs = [p.grad for p in ctx.params[:nb]] if direct else [torch.empty_like(g) for g in gammas]
+        dbs = [p.grad for p in ctx.params[nb:]] if direct else [torch.empty_like(g) for g in gammas]
+        cells = torch.empty(nb, dtype=torch.int32, device=dy.device) if FUSE_ABSMAX else None
+        br = (_lib.BncBranch * nb)(*[
+            _lib.BncBranch(x.data_ptr(), g.data_ptr(), None, None, None, None, dx.data_ptr(), dg.data_ptr(), db.data_ptr(),
+                           None if cells is None else cells[i:i + 1].data_ptr(), c, 0)
+            for i, (x, g, dx, dg, db, c) in enumerate(zip(xs, gammas, dxs, dgs, dbs, cs))])
+        wsp = _workspace(dy.device, lib.cstp_bnrelu_concat_workspace_bytes(sum(cs), groups))
+        with _span("bnc_backward", (n, s, groups, tuple(cs))):
+            check(lib.cstp_bnrelu_concat_backward(_stream(), br, nb, n, s, groups, dy.data_ptr(), mean.data_ptr(),
+                                                  invstd.data_ptr(), ss.data_ptr(), wsp.data_ptr(), wsp.numel(),
+                                                  1 if direct else 0), "cstp_bnrelu_concat_backward")
+        if cells is not None:
+            for i, dx in enumerate(dxs):
+                _tag_absmax(dx, cells[i:i + 1])
+        head = (None,) * 6
+        if direct:
+            return head + tuple(dxs) + (None,) * (2 * nb)
+        return head + tuple(dxs) + tuple(dgs) + tuple(dbs)
+
+
+def _bnc_check(branches, bns):
+    branches, bns = list(branches), [tuple(b) for b in bns]
+    if not 1 <= len(branches) <= 4 or len(bns) != len(branches) or any(len(b) != 4 for b in bns):
+        raise _lib.CstpError("bn_relu_concat takes 1..4 branches with one (weight, bias, running_mean, running_var) each, got "
+                             "%d and %d" % (len(branches), len(bns)))
+    for t in branches + [b[0] for b in bns] + [b[1] for b in bns]:
+        if t.dtype == torch.bfloat16:
+            raise _lib.CstpError("bn_relu_concat is fp32 only (I3D has no bf16-storage path)")
+    return branches, bns
+
+
+def bn_relu_concat(branches, bns, groups=1, eps=BN_EPS, momentum=BN_MOMENTUM):
+    """I3D Mixed tail (fp32): ``torch.cat([relu(batch_norm_train(x, ...)) for x in branches], 1)`` with ``bns`` the
+    (weight, bias, running_mean, running_var) of each branch's BatchNorm3d; the running statistics are updated in place
+    (``groups`` > 1: group after group, as batch_norm_act).  A branch whose convolution left its partial sums (ops.conv3d(...,
+    bn_groups=groups)) uses them -- the result then equals batch_norm_act + cat bit for bit -- the others share one statistics
+    launch.  The result is tagged with its max |y| cell for the 1x1x1 convolutions that consume it."""
+    branches, bns = _bnc_check(branches, bns)
+    nb = len(branches)
+    gammas, betas = [b[0] for b in bns], [b[1] for b in bns]
+    running = [(None if b[2] is None else _req(b[2], "running_mean"), None if b[3] is None else _req(b[3], "running_var"))
+               for b in bns]
+    save = torch.is_grad_enabled() and any(t.requires_grad for t in branches + gammas + betas)
+    _BNReluConcat._pre_stats = [_bnstats_of(x, int(groups)) for x in branches]
+    y = _BNReluConcat.apply(nb, save, int(groups), float(eps), float(momentum), running, *branches, *gammas, *betas)
+    _tag_absmax(y, _BNReluConcat._last_cell)
+    _BNReluConcat._last_cell = None
+    return y
+
+
+def bn_relu_concat_eval(branches, bns, eps=BN_EPS):
+    """model.eval() form of bn_relu_concat: ``torch.cat([relu(batch_norm_eval(x, ...)) for x in branches], 1)`` (running
+    statistics, nothing updated).  Forward only, as batch_norm_eval."""
+    lib = _lib.load()
+    branches, bns = _bnc_check(branches, bns)
+    if torch.is_grad_enabled() and any(t.requires_grad for t in branches + [b[0] for b in bns] + [b[1] for b in bns]):
+        raise _lib.CstpError("eval-mode BatchNorm is forward-only: call it under torch.no_grad() (as the reference's "
+                             "validation/test loops do)")
+    xs = [_req(x, "bn_relu_concat branch") for x in branches]
+    n, spatial = xs[0].shape[0], tuple(xs[0].shape[2:])
+    if any(x.dim() != 5 or x.shape[0] != n or tuple(x.shape[2:]) != spatial for x in xs):
+        raise _lib.CstpError("bn_relu_concat branches must be [N, C_i, D, H, W] with one N, D, H, W; got %s"
+                             % ([tuple(t.shape) for t in xs],))
+    cs = [x.shape[1] for x in xs]
+    ctot = sum(cs)
+    s = xs[0].numel() // (n * cs[0])
+    y = torch.empty((n, ctot) + spatial, dtype=torch.float32, device=xs[0].device)
+    ss = torch.empty(ctot * 2, dtype=torch.float32, device=y.device)
+    cell = _new_cell(y)
+    keep = [[_req(t, "BatchNorm tensor") for t in b] for b in bns]
+    br = (_lib.BncBranch * len(xs))(*[
+        _lib.BncBranch(x.data_ptr(), k[0].data_ptr(), k[1].data_ptr(), k[2].data_ptr(), k[3].data_ptr(), None, None, None, None,
+                       None, c, 0) for x, k, c in zip(xs, keep, cs)])
+    check(lib.cstp_bnrelu_concat_eval(_stream(), br, len(xs), n, s, float(eps), y.data_ptr(), ss.data_ptr(), _ptr(cell)),
+          "cstp_bnrelu_concat_eval")
+    _tag_absmax(y, cell)
+    return y
+
+
+# ----------------------------------------------------------------------------------------------
 # the bf16-STORAGE path (csrc/b16.hip; BASELINE configs[4]), selected by the dtype of the activation tensor:
 # 5-D activations and their gradients bf16, parameters / their gradients / statistics fp32 (cstp_hip.h "bf16-STORAGE path")
 # ----------------------------------------------------------------------------------------------

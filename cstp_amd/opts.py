@@ -29,9 +29,9 @@ _FLAGS = [
     ("n_classes", 400, int, "number of classes"),
     ("n_finetune_classes", 51, int, "number of classes when fine-tuning"),
     # model
-    ("model_name", "resnext", str, "backbone (this package: r21d_byol | r3d_byol | s3d_byol)"),
+    ("model_name", "resnext", str, "backbone (this package: r21d_byol | r3d_byol | s3d_byol | i3d_byol)"),
     ("model_depth", 101, int, "r21d_byol: 1 -> (1,1,1,1), 18 -> (2,2,2,2), 34 -> (3,4,6,3); r3d_byol: 10..152; "
-                                        "s3d_byol: ignored (only names the checkpoint arch)"),
+                                        "s3d_byol / i3d_byol: ignored (only names the checkpoint arch)"),
     ("resnet_shortcut", "B", str, "shortcut type of resnet (A | B)"),
     ("resnext_cardinality", 32, int, "ResNeXt cardinality"),
     ("ft_begin_index", 0, int, "first block to fine-tune"),
@@ -90,7 +90,7 @@ _FLAGS = [
     ("synthetic_len", 256, int, "samples per epoch for --dataset synthetic"),
     ("max_steps", 0, int, "stop each epoch after this many iterations (0 = all)"),
     ("bucket_cap_mb", 25, int, "DDP gradient bucket size in MB"),
-    ("act_dtype", "fp32", str, "fp32 | bf16: activation storage type (r21d_byol and r3d_byol; s3d_byol is fp32 only)"),
+    ("act_dtype", "fp32", str, "fp32 | bf16: activation storage type (r21d_byol and r3d_byol; s3d_byol and i3d_byol are fp32 only)"),
 ]
 
 

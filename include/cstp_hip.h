@@ -480,6 +480,58 @@ size_t cstp_gate_workspace_bytes(int32_t n, int32_t ctot);
 int cstp_gate_concat_backward(void* stream, const cstp_gate_branch* branches, int32_t nbranch, int32_t n, int32_t s,
                               const float* dy, const float* m, const float* g, void* ws, size_t ws_bytes, int32_t accumulate);
 
+/* ---- I3D: TensorFlow-SAME max-pool, the inception tail, the fine-tune head's average pool (csrc/mixed.hip) ----------------
+ * SAME max-pool (models/BE/i3d_byol.py:170-183): MaxPool3d(k, s, ceil_mode=True) over ConstantPad3d(get_padding_shape(k, s), 0)
+ * without the padded copy.  Per dimension pad = max(k - s, 0), front = pad / 2, the rest behind; output length
+ * cstp_maxpool3d_same_out(n, k, s) = ceil((n + pad - k) / s) + 1, one less if the last window would start at or beyond n + pad.
+ * A window position in the padding is a candidate of value 0, one beyond the padded extent is none; scan order, the strict `>`
+ * tie rule and the NaN rule are those of cstp_maxpool3d_forward.  argmax (int32, may be NULL in forward) holds the flat index
+ * in the UNPADDED (d, h, w) volume, or -1 where a padding zero won (its gradient is dropped).  backward gathers (no atomics). */
+int cstp_maxpool3d_same_out(int32_t n, int32_t k, int32_t s);
+int cstp_maxpool3d_same_forward(void* stream, const float* x, float* y, int32_t* argmax, int32_t rows, int32_t d, int32_t h,
+                                int32_t w, const int32_t* kernel3, const int32_t* stride3);
+int cstp_maxpool3d_same_backward(void* stream, const float* dy, const int32_t* argmax, float* dx, int32_t rows, int32_t d,
+                                 int32_t h, int32_t w, const int32_t* kernel3, const int32_t* stride3);
+/* nn.AvgPool3d(kernel, stride 1) over valid windows (i3d_byol.py:297): x [rows][d][h][w] -> y [rows][d-kd+1][h-kh+1][w-kw+1]. */
+int cstp_avgpool3d_window_forward(void* stream, const float* x, float* y, int32_t rows, int32_t d, int32_t h, int32_t w,
+                                  const int32_t* kernel3);
+int cstp_avgpool3d_window_backward(void* stream, const float* dy, float* dx, int32_t rows, int32_t d, int32_t h, int32_t w,
+                                   const int32_t* kernel3);
+/* Mixed tail (i3d_byol.py:214-220 with :159-167 of each branch's last Unit3Dpy): train-mode BatchNorm3d + ReLU of up to four
+ * branches written straight into channels [o_i, o_i + c_i) of the concat tensor y [n][C][s].  Branch i: x_i [n][c_i][s], the raw
+ * output of its last convolution.  part != NULL: the table cstp_conv3d_forward_bnstats left beside x_i ([c][groups][nsplit][2]
+ * sums around the pivots behind them); the statistics then take the arithmetic of cstp_bn_forward_train_pre and y equals
+ * cstp_bn_forward_train_pre + concatenation bit for bit.  part == NULL: one statistics launch covers every such branch.
+ * save_mean / save_invstd [groups][C] and scale_shift [groups][C][2] are indexed by CONCAT channel.  Launches: finalize + apply
+ * (+ statistics).  No float atomics: a second call gives the same bits. */
+typedef struct cstp_bnc_branch {
+  const float* x;          /* [n][c][s] */
+  const float* gamma;      /* [c] */
+  const float* beta;       /* [c]; not read by backward (may be NULL there) */
+  float* running_mean;     /* [c], updated by the train forward; with running_var, or both NULL */
+  float* running_var;
+  const double* part;      /* train forward: the producing convolution's partial sums, or NULL */
+  float* dx;               /* backward: [n][c][s] */
+  float* dgamma;           /* backward: [c] */
+  float* dbeta;            /* backward: [c] */
+  uint32_t* dx_absmax;     /* backward, optional: max |dx_i| as fp32 bits */
+  int32_t c;
+  int32_t nsplit;          /* of part */
+} cstp_bnc_branch;
+#define CSTP_BNC_MAX_BRANCHES 4
+size_t cstp_bnrelu_concat_workspace_bytes(int32_t ctot, int32_t groups);
+int cstp_bnrelu_concat_forward(void* stream, const cstp_bnc_branch* branches, int32_t nbranch, int32_t n, int32_t s,
+                               int32_t groups, float eps, float momentum, float* y, float* save_mean, float* save_invstd,
+                               float* scale_shift, void* ws, size_t ws_bytes, uint32_t* y_absmax);
+/* model.eval(): the running statistics are the statistics (cstp_bn_forward_eval per branch + concatenation); two launches. */
+int cstp_bnrelu_concat_eval(void* stream, const cstp_bnc_branch* branches, int32_t nbranch, int32_t n, int32_t s, float eps,
+                            float* y, float* scale_shift, uint32_t* y_absmax);
+/* Backward, two launches: dy [n][C][s] of the whole concat tensor is read through each branch's channel offset; the ReLU mask is
+ * recomputed from x_i and scale_shift.  accumulate != 0: dgamma / dbeta are ADDED to (a flat gradient arena), else written. */
+int cstp_bnrelu_concat_backward(void* stream, const cstp_bnc_branch* branches, int32_t nbranch, int32_t n, int32_t s,
+                                int32_t groups, const float* dy, const float* save_mean, const float* save_invstd,
+                                const float* scale_shift, void* ws, size_t ws_bytes, int32_t accumulate);
+
 #ifdef __cplusplus
 }
 #endif
