@@ -129,6 +129,9 @@ SIGNATURES = {
     "cstp_clip_gray": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, _P]),
     "cstp_clip_box_blur": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_uint32, c_uint32, c_int32]),
     "cstp_clip_finish": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32]),
+    "cstp_clip_batch_desc_bytes": (c_size_t, []),
+    "cstp_clip_batch_forward": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, _P, c_int32, _P, c_int64, _P, c_int32, _P,
+                                          c_int32]),
     "cstp_ema_update": (c_int32, [_P, _P, _P, c_size_t, c_double]),
     "cstp_sumsq": (c_int32, [_P, _P, c_size_t, _P, _P, c_size_t]),
     "cstp_clip_coef": (c_int32, [_P, _P, c_float, _P, _P]),

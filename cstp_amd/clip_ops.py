@@ -7,6 +7,10 @@ Replaces the reference's per-worker PIL pipeline, both its `null_transform` path
 rotation, colour jitter, channel gray, Gaussian blur on the resized 8-bit frames: preprocess_data.py:1110-1121) -- (Image.open -> transpose -> crop -> resize ->
 flip -> ToTensor -> normalise on the CPU, 6 DataLoader workers per GPU, preprocess_data.py:1103-1130): the frames are uploaded
 once as uint8 and every clip is produced where it is consumed.  There is no CPU implementation here.
+
+The fine-tune / validation / video-test side (UcfFineTune, datasets.py:952-1097, under the 'img' / 'img_val' / 'img_test' transforms)
+is the second half of this file: ``assemble_batch`` (cstp_clip_batch_forward: a whole batch or test video in two launches),
+``GpuLabelledVideos`` and ``GpuLabelledLoader``.
 """
 from __future__ import annotations
 
@@ -311,3 +315,200 @@ class GpuClipLoader:
         for b in range(len(self)):
             c1, c2, spa, tem, pb, r1, r2 = self.dataset.batch(idx[b * self.batch_size:(b + 1) * self.batch_size])
             yield [c1, c2], [spa, tem, pb, [r1, r2]]
+
+
+# ---- batched assembly (libcstp_hip.so: cstp_clip_batch_forward) and the fine-tune / validation / video-test data path ----------
+# struct cstp_clip_batch_desc (include/cstp_hip.h), packed by hand into the pinned upload buffer
+_BATCH_DESC = np.dtype([(n, "<u8") for n in ("frames", "kh", "bh", "kv", "bv")] + [("tmp_off", "<i8")]
+                       + [(n, "<i4") for n in ("f", "h", "w", "idx_off", "box_x0", "box_y0", "ksh", "ksv", "rw", "rh", "win_x",
+                                               "win_y", "row_first", "rows", "flip", "out_slot", "out8_slot", "reserved")])
+
+
+def window_rows(in_size: int, out_size: int, origin: int, size: int):
+    """(first, count) of the input rows that the vertical taps of output rows [origin, origin + size) read."""
+    _, b, _ = resize_tables(in_size, out_size)
+    first = int(b[origin, 0])
+    return first, int(b[origin + size - 1, 0] + b[origin + size - 1, 1]) - first
+
+
+def assemble_batch(videos, plans, size: int, out: torch.Tensor = None) -> torch.Tensor:
+    """A whole batch of clips in two launches: plans[i] (``sampler.FtClipPlan``, or any plan with ``frames`` and ``box``; optional
+    ``resized`` (w, h), ``window`` (x, y), ``jitter``, ``flip``) cut from videos[i] (uint8 [F][H][W][3] on one HIP device; a single
+    tensor serves every plan) -> fp32 [B][3][T][size][size], written straight into the batch tensor (``out``, if given).  Clips
+    may come from videos of different frame sizes.  Descriptors and frame indices travel in ONE pinned upload; nothing is
+    allocated per clip.  Clips with colour jitter leave the resize as 8-bit frames and go on through cstp_clip_blend / _hue /
+    _finish, one transform per clip (ClipColorJitter)."""
+    lib = _lib.load()
+    plans = list(plans)
+    n = len(plans)
+    if n == 0:
+        raise ValueError("assemble_batch needs at least one plan")
+    if torch.is_tensor(videos):
+        videos = [videos] * n
+    if len(videos) != n:
+        raise ValueError("%d videos for %d plans" % (len(videos), n))
+    if lib.cstp_clip_batch_desc_bytes() != _BATCH_DESC.itemsize:
+        raise _lib.CstpError("cstp_clip_batch_desc is %d bytes in the library, %d here"
+                             % (lib.cstp_clip_batch_desc_bytes(), _BATCH_DESC.itemsize))
+    dev = videos[0].device
+    t = len(plans[0].frames)
+    jittered = [i for i, p in enumerate(plans) if getattr(p, "jitter", None)]
+    slot8 = {i: j for j, i in enumerate(jittered)}
+    nbytes = n * _BATCH_DESC.itemsize + 4 * n * t
+    host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
+    view = host.numpy()
+    desc = view[:n * _BATCH_DESC.itemsize].view(_BATCH_DESC)
+    idx = view[n * _BATCH_DESC.itemsize:].view(np.int32)
+    tmp_pixels = 0
+    for i, (v, p) in enumerate(zip(videos, plans)):
+        if not v.is_cuda or v.dtype != torch.uint8 or v.dim() != 4 or v.shape[3] != 3 or not v.is_contiguous() or v.device != dev:
+            raise _lib.CstpError("videos must be contiguous uint8 [F, H, W, 3] tensors on one HIP device (cstp_amd has no CPU path)")
+        if len(p.frames) != t:
+            raise ValueError("clips of %d and %d frames in one batch" % (t, len(p.frames)))
+        if getattr(p, "rotate", 0) or getattr(p, "base", None) is not None:
+            raise ValueError("assemble_batch serves crop / scale / window / jitter plans; rotated and base_transform clips go "
+                             "through assemble_clip")
+        x0, y0, x1, y1 = p.box
+        if not (x0 < x1 and y0 < y1):
+            raise _lib.CstpError("empty crop box %s" % (p.box,))
+        rw, rh = getattr(p, "resized", (size, size))
+        wx, wy = getattr(p, "window", (0, 0))
+        if wx < 0 or wy < 0 or wx + size > rw or wy + size > rh:
+            raise ValueError("window (%d, %d) + %d leaves the %d x %d resized image" % (wx, wy, size, rw, rh))
+        ksh, bh, kh, _, _ = _device_tables(x1 - x0, rw, dev)
+        ksv, bv, kv, _, _ = _device_tables(y1 - y0, rh, dev)
+        first, rows = window_rows(y1 - y0, rh, wy, size)
+        f, h, w, _ = v.shape
+        desc[i] = (v.data_ptr(), kh.data_ptr(), bh.data_ptr(), kv.data_ptr(), bv.data_ptr(), tmp_pixels, f, h, w, i * t, x0, y0,
+                   ksh, ksv, rw, rh, wx, wy, first, rows, 1 if getattr(p, "flip", False) else 0,
+                   -1 if i in slot8 else i, slot8.get(i, -1), 0)
+        idx[i * t:(i + 1) * t] = p.frames
+        tmp_pixels += t * rows * size
+    if out is None:
+        out = torch.empty((n, 3, t, size, size), dtype=torch.float32, device=dev)
+    elif out.shape != (n, 3, t, size, size) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+        raise ValueError("out must be a contiguous fp32 [%d, 3, %d, %d, %d] tensor on %s" % (n, t, size, size, dev))
+    table = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    table.copy_(host, non_blocking=True)
+    tmp = torch.empty(tmp_pixels * 3, dtype=torch.uint8, device=dev)
+    u8 = torch.empty((len(jittered), t, size, size, 3), dtype=torch.uint8, device=dev) if jittered else None
+    st = torch.cuda.current_stream().cuda_stream
+    check(lib.cstp_clip_batch_forward(st, table.data_ptr(), host.data_ptr(), n, t, size,
+                                      table.data_ptr() + n * _BATCH_DESC.itemsize, n * t, tmp.data_ptr(), tmp_pixels,
+                                      out.data_ptr(), n, None if u8 is None else u8.data_ptr(), len(jittered)),
+          "cstp_clip_batch_forward")
+    for i in jittered:
+        clip = u8[slot8[i]]
+        for op, factor in plans[i].jitter:
+            clip = clip_colour(clip, op, factor)
+        check(lib.cstp_clip_finish(st, clip.data_ptr(), out[i].data_ptr(), t, size, size, 1 if getattr(plans[i], "flip", False) else 0),
+              "cstp_clip_finish")
+    return out
+
+
+def _labelled_video(label: int, n_classes: int, frames: int, height: int, width: int, gen, device) -> torch.Tensor:
+    """uint8 [F][H][W][3]: a moving grating whose orientation, frequency, drift and colour phase are functions of the label,
+    plus uniform noise -- separable by a classifier, and smooth enough that a resize is not all aliasing."""
+    ang = math.pi * label / max(n_classes, 1)
+    freq = 2.0 + (label % 4)
+    drift = 0.5 * (1 + (label // 4) % 3)
+    ys = torch.linspace(-1, 1, height, device=device).view(1, height, 1, 1)
+    xs = torch.linspace(-1, 1, width, device=device).view(1, 1, width, 1)
+    ts = torch.arange(frames, device=device, dtype=torch.float32).view(frames, 1, 1, 1) / 32.0
+    ch = torch.tensor([0.0, 2.1, 4.2], device=device).view(1, 1, 1, 3) * (1 + label % 3) / 3.0
+    phase = freq * math.pi * (math.cos(ang) * xs + math.sin(ang) * ys) + 2 * math.pi * drift * ts + ch
+    img = 0.5 + 0.35 * torch.sin(phase) + 0.15 * (torch.rand((frames, height, width, 3), generator=gen, device=device) - 0.5)
+    return (img.clamp(0, 1) * 255).to(torch.uint8).contiguous()
+
+
+class GpuLabelledVideos:
+    """Stands in for UcfFineTune (datasets.py:952-1097) on synthetic data: ``n_videos`` labelled, decoded videos (uint8 frames,
+    class-dependent patterns, 240 x 320 by default so ClipScale really resizes) live in HBM, with mixed lengths -- the first is
+    shorter than clip_range + 1 and takes the wrap-around branch, the second is exactly clip_range + 1.  'train' / 'val' items
+    are one clip under ``mode`` ('img' / 'img_val'); a 'test' item is every clip of a video under 'img_test'.  Each sample's RNG
+    is seeded from (seed, epoch, index), so the augmentation of a video changes from epoch to epoch.  Selected by the fine-tune
+    and test drivers with ``--dataset synthetic_video``."""
+
+    _SALT = {"train": 11, "val": 23, "test": 37}
+
+    def __init__(self, device, data_type="train", mode="img", n_videos=8, n_classes=101, height=240, width=320, sample_duration=16,
+                 sample_size=112, pb_rate=4, length=None, seed=1, lengths=None):
+        if data_type not in self._SALT:
+            raise ValueError("data_type %r" % (data_type,))
+        sampler._check_ft_mode(mode)
+        if (data_type == "test") != (mode == "img_test"):
+            raise ValueError("data_type %r with transform mode %r: the video test takes 'img_test', train / val take 'img' / "
+                             "'img_val'" % (data_type, mode))
+        if mode != "img":
+            sampler.short_side(sample_size)
+        self.device, self.data_type, self.mode = torch.device(device), data_type, mode
+        self.t, self.size, self.pb_rate, self.seed, self.n_classes = sample_duration, sample_size, pb_rate, seed, n_classes
+        clip_range = (sample_duration - 1) * pb_rate
+        if lengths is None:
+            cycle = [max(clip_range - 3, 2), clip_range + 1, 2 * clip_range + 7, clip_range + clip_range // 2, 3 * clip_range + 5]
+            lengths = [cycle[v % len(cycle)] for v in range(n_videos)]
+        salt = self._SALT[data_type]
+        g = torch.Generator(device=self.device).manual_seed(seed * 101 + salt)
+        self.labels = [(v * 7 + salt) % n_classes for v in range(len(lengths))]
+        self.videos = [_labelled_video(lab, n_classes, int(f), height, width, g, self.device)
+                       for lab, f in zip(self.labels, lengths)]
+        self.length = len(self.videos) if length is None else length
+
+    def __len__(self):
+        return self.length
+
+    def plan(self, index: int, epoch: int = 0):
+        """-> (video number, FtClipPlan) for 'train' / 'val', (video number, [FtClipPlan]) for 'test'."""
+        v = index % len(self.videos)
+        f, h, w, _ = self.videos[v].shape
+        if self.data_type == "test":
+            return v, sampler.plan_test_video(f, w, h, self.t, self.size, self.pb_rate, self.mode)
+        rng = random.Random(((self.seed * 1000003 + epoch) * 1000003 + index) * 101 + self._SALT[self.data_type])
+        return v, sampler.sample_ft_clip(f, w, h, self.t, self.size, self.pb_rate, self.mode, rng)
+
+    def _labels(self, vs):
+        return torch.tensor([self.labels[v] for v in vs], dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)
+
+    def batch(self, indices: List[int], epoch: int = 0):
+        """-> (clips [B,3,T,S,S] fp32, labels [B] int64) on the device."""
+        picked = [self.plan(i, epoch) for i in indices]
+        clips = assemble_batch([self.videos[v] for v, _ in picked], [p for _, p in picked], self.size)
+        return clips, self._labels([v for v, _ in picked])
+
+    def video(self, index: int):
+        """A 'test' item: (clips [n_clips,3,T,S,S] fp32, label [1] int64) on the device (datasets.py:999-1001)."""
+        if self.data_type != "test":
+            raise ValueError("video() serves data_type 'test'")
+        v, plans = self.plan(index)
+        return assemble_batch(self.videos[v], plans, self.size), self._labels([v])
+
+
+class GpuLabelledLoader(GpuClipLoader):
+    """GpuClipLoader's sharding for GpuLabelledVideos.  'train': epoch-seeded shuffle, this rank's stride, full batches only;
+    'val': in order, the last partial batch kept (utils.py:91-163); 'test': one video per item, ``(clips [1,n_clips,3,T,S,S],
+    label [1])`` as DataLoader(batch_size=1) collates it (test.py:58-60).  Batches are born on the device."""
+
+    def __init__(self, dataset: GpuLabelledVideos, batch_size: int = 1, rank: int = 0, world_size: int = 1, seed: int = 0):
+        super().__init__(dataset, batch_size, rank, world_size, seed)
+        self.data_type = dataset.data_type
+
+    def indices(self) -> List[int]:
+        if self.data_type == "train":
+            return super().indices()
+        return list(range(len(self.dataset)))[self.rank::self.world_size]
+
+    def __len__(self):
+        if self.data_type == "train":
+            return super().__len__()
+        n = len(self.indices())
+        return n if self.data_type == "test" else (n + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        idx = self.indices()
+        if self.data_type == "test":
+            for i in idx:
+                clips, label = self.dataset.video(i)
+                yield clips.unsqueeze(0), label
+            return
+        for b in range(len(self)):
+            yield self.dataset.batch(idx[b * self.batch_size:(b + 1) * self.batch_size], self.epoch)

@@ -10,6 +10,8 @@
 // Image.crop does), the flip and the normalisation into the store of the vertical pass, so a frame is read
 // once and the clip is written once; both kernels are HBM/latency-trivial next to a training step (a 16-frame 112x112 clip from
 // 240x320 frames: 3.7 MB in, 2.4 MB out).
+// The fine-tune / validation / video-test clips (datasets.py:952-1097 UcfFineTune, preprocess_data.py:1131-1149) come a BATCH at a
+// time through cstp_clip_batch_forward at the end of this file: one descriptor table, two launches for any number of clips.
 #include "common.h"
 
 namespace cstp {
@@ -379,6 +381,134 @@ extern "C" int cstp_clip_finish(void* stream, const uint8_t* src, float* out, in
   CSTP_REQUIRE(t > 0 && h > 0 && w > 0, "bad shape");
   hipLaunchKernelGGL(clip_finish_kernel, dim3(clip_grid((size_t)t * h * w)), dim3(256), 0, as_stream(stream), src, out, t, h, w,
                      flip ? 1 : 0);
+  CSTP_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- batched, descriptor-driven assembly (cstp_clip_batch_forward): the fine-tune / validation / video-test data path -------
+// A whole batch -- clips of different videos, frame sizes, boxes and scales -- in two launches: blockIdx.y picks the clip's
+// descriptor, blockIdx.x strides over that clip's pixels.  The arithmetic is that of clip_resize_h_kernel / clip_resize_v_kernel
+// (no rotation on this path); new is the output WINDOW: of the resized rw x rh image only the size x size window at
+// (win_x, win_y) is produced, so ClipScale -> ClipCenterCrop (240x320 -> 128x170 -> 112x112) computes 112 of 170 columns and
+// only the tmp rows the window's vertical taps read, and the result still equals resize-then-crop bit for bit because an output
+// pixel depends on its own taps alone.
+// What bounds them: gather latency, not bandwidth.  A batch of 32 clips of 16 frames from 240x320 frames reads at most 118 MB of
+// frames and writes 77 MB of fp32 (~30 us at the HBM rate); every output pixel instead walks 5..13 taps of 3 bytes behind two
+// dependent table loads (bounds, then coefficients), so the passes run at the rate the L1 / L2 return those short reads -- the
+// lanes of a wave read neighbouring output columns, whose tap spans overlap, and the vertical pass reads tmp rows that 64 lanes
+// share coalesced.  Tables (at most a few KiB per axis) and descriptors stay in the scalar / L2 caches.  Next to a training step
+// the two launches are noise; what the batching removes is the 2+ launches, the blocking index upload and the allocation PER CLIP.
+namespace cstp {
+
+__global__ void __launch_bounds__(256) clip_batch_h_kernel(const cstp_clip_batch_desc* __restrict__ descs,
+                                                           const int32_t* __restrict__ frame_idx, uint8_t* __restrict__ tmp,
+                                                           int T, int size) {
+  const cstp_clip_batch_desc d = descs[blockIdx.y];
+  const size_t total = (size_t)T * d.rows * size;
+  uint8_t* const tp = tmp + (size_t)d.tmp_off * 3;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int xx = (int)(i % size);
+    const size_t r = i / size;
+    const int y = (int)(r % d.rows), t = (int)(r / d.rows);
+    int f = frame_idx[d.idx_off + t];
+    f = f < 0 ? 0 : (f >= d.f ? d.f - 1 : f);
+    const int cx = d.win_x + xx;                           // column of the resized image
+    const int x0 = d.bh[2 * cx];
+    int n = d.bh[2 * cx + 1];
+    n = n > d.ksh ? d.ksh : n;
+    const int oy = d.box_y0 + d.row_first + y;             // row in the frame
+    int a0 = 1 << (CLIP_PRECISION_BITS - 1), a1 = a0, a2 = a0;
+    if (oy >= 0 && oy < d.h) {                             // Image.crop beyond the frame reads black (0, 0, 0)
+      const uint8_t* row = d.frames + ((size_t)f * d.h + oy) * d.w * 3;
+      const int32_t* k = d.kh + (size_t)cx * d.ksh;
+      for (int j = 0; j < n; ++j) {
+        const int ox = d.box_x0 + x0 + j;
+        if (ox < 0 || ox >= d.w) continue;
+        const uint8_t* p = row + (size_t)ox * 3;
+        const int kj = k[j];
+        a0 += (int)p[0] * kj; a1 += (int)p[1] * kj; a2 += (int)p[2] * kj;
+      }
+    }
+    uint8_t* o = tp + i * 3;
+    o[0] = (uint8_t)clip8_fixed(a0); o[1] = (uint8_t)clip8_fixed(a1); o[2] = (uint8_t)clip8_fixed(a2);
+  }
+}
+
+__global__ void __launch_bounds__(256) clip_batch_v_kernel(const cstp_clip_batch_desc* __restrict__ descs,
+                                                           const uint8_t* __restrict__ tmp, float* __restrict__ out,
+                                                           uint8_t* __restrict__ out8, int T, int size) {
+  const cstp_clip_batch_desc d = descs[blockIdx.y];
+  const size_t total = (size_t)T * size * size;
+  const uint8_t* const tp = tmp + (size_t)d.tmp_off * 3;
+  const size_t plane = total;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int xx = (int)(i % size);
+    const size_t r = i / size;
+    const int yy = (int)(r % size), t = (int)(r / size);
+    const int cy = d.win_y + yy;                           // row of the resized image
+    const int y0 = d.bv[2 * cy] - d.row_first;
+    int n = d.bv[2 * cy + 1];
+    n = n > d.ksv ? d.ksv : n;
+    const int32_t* k = d.kv + (size_t)cy * d.ksv;
+    int a0 = 1 << (CLIP_PRECISION_BITS - 1), a1 = a0, a2 = a0;
+    for (int j = 0; j < n; ++j) {
+      const int ry = y0 + j;
+      if (ry < 0 || ry >= d.rows) continue;                // never taken with consistent tables; keeps a bad table inside tmp
+      const uint8_t* p = tp + (((size_t)t * d.rows + ry) * size + xx) * 3;
+      const int kj = k[j];
+      a0 += (int)p[0] * kj; a1 += (int)p[1] * kj; a2 += (int)p[2] * kj;
+    }
+    const int c8[3] = {clip8_fixed(a0), clip8_fixed(a1), clip8_fixed(a2)};
+    if (d.out8_slot >= 0) {                                // 8-bit RGB for the colour-jitter kernels: no flip, no normalisation
+      uint8_t* o8 = out8 + ((size_t)d.out8_slot * plane + i) * 3;
+      o8[0] = (uint8_t)c8[0]; o8[1] = (uint8_t)c8[1]; o8[2] = (uint8_t)c8[2];
+      continue;
+    }
+    const int xo = d.flip ? size - 1 - xx : xx;
+    float* o = out + (size_t)d.out_slot * 3 * plane + ((size_t)t * size + yy) * size + xo;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      float v = (float)c8[c] / 255.0f;                     // transforms.ToTensor()
+      v = v * 2.0f - 1.0f;                                 // ClipNormalize('tf')
+      o[c * plane] = fminf(fmaxf(v, -1.0f), 1.0f);
+    }
+  }
+}
+
+}  // namespace cstp
+
+extern "C" size_t cstp_clip_batch_desc_bytes(void) { return sizeof(cstp_clip_batch_desc); }
+
+extern "C" int cstp_clip_batch_forward(void* stream, const cstp_clip_batch_desc* desc_dev, const cstp_clip_batch_desc* desc_host,
+                                       int32_t n, int32_t t, int32_t size, const int32_t* frame_idx, int32_t n_idx, uint8_t* tmp,
+                                       int64_t tmp_pixels, float* out, int32_t out_slots, uint8_t* out8, int32_t out8_slots) {
+  static_assert(sizeof(cstp_clip_batch_desc) == 120, "cstp_clip_batch_desc is packed by the host as 120 bytes");
+  CSTP_REQUIRE(desc_dev && desc_host && frame_idx && tmp, "null argument");
+  CSTP_REQUIRE(n > 0 && n <= 65535 && t > 0 && size > 0 && size <= 4096 && n_idx > 0 && tmp_pixels > 0, "bad shape");
+  CSTP_REQUIRE(out_slots >= 0 && out8_slots >= 0 && (out || out_slots == 0) && (out8 || out8_slots == 0), "bad output");
+  size_t most_h = 0;
+  for (int i = 0; i < n; ++i) {      // every offset the kernels form from a descriptor is checked here, against the sizes given
+    const cstp_clip_batch_desc& d = desc_host[i];
+    CSTP_REQUIRE(d.frames && d.kh && d.bh && d.kv && d.bv, "null pointer in a descriptor");
+    CSTP_REQUIRE(d.f > 0 && d.h > 0 && d.w > 0 && d.h < 32768 && d.w < 32768, "bad frame shape in a descriptor");
+    CSTP_REQUIRE(d.idx_off >= 0 && (int64_t)d.idx_off + t <= n_idx, "frame indices of a descriptor leave the index array");
+    CSTP_REQUIRE(d.ksh > 0 && d.ksv > 0 && d.rw > 0 && d.rh > 0, "bad table shape in a descriptor");
+    CSTP_REQUIRE(d.win_x >= 0 && d.win_y >= 0 && (int64_t)d.win_x + size <= d.rw && (int64_t)d.win_y + size <= d.rh,
+                 "output window of a descriptor leaves the resized image");
+    CSTP_REQUIRE(d.row_first >= 0 && d.rows > 0 && d.rows < 32768, "bad tmp rows in a descriptor");
+    CSTP_REQUIRE(d.tmp_off >= 0 && d.tmp_off + (int64_t)t * d.rows * size <= tmp_pixels, "tmp of a descriptor leaves the buffer");
+    CSTP_REQUIRE((d.out_slot >= 0) != (d.out8_slot >= 0), "a descriptor needs exactly one of out_slot / out8_slot");
+    CSTP_REQUIRE(d.out_slot < out_slots && d.out8_slot < out8_slots, "output slot of a descriptor leaves its buffer");
+    const size_t items = (size_t)t * d.rows * size;
+    most_h = items > most_h ? items : most_h;
+  }
+  hipStream_t s = as_stream(stream);
+  const size_t bh_ = (most_h + 255) / 256, bv_ = ((size_t)t * size * size + 255) / 256;
+  hipLaunchKernelGGL(clip_batch_h_kernel, dim3((unsigned)(bh_ > 2048 ? 2048 : bh_), n), dim3(256), 0, s, desc_dev, frame_idx, tmp, t,
+                     size);
+  CSTP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(clip_batch_v_kernel, dim3((unsigned)(bv_ > 2048 ? 2048 : bv_), n), dim3(256), 0, s, desc_dev, tmp, out, out8, t,
+                     size);
   CSTP_LAUNCH_CHECK();
   return 0;
 }

@@ -22,7 +22,8 @@ _FLAGS = [
     # datasets
     ("frame_dir", "dataset/HMDB51/", str, "path of jpg files"),
     ("annotation_path", "dataset/HMDB51_labels", str, "label paths"),
-    ("dataset", "HMDB51", str, "HMDB51 | UCF101 | Kinetics | synthetic | synthetic_video"),
+    ("dataset", "HMDB51", str, "HMDB51 | UCF101 | Kinetics | synthetic | synthetic_video (HBM-resident videos, clips assembled on the GPU: "
+     "pre-training, fine-tuning with --transform_mode img, video test with --transform_mode img_test)"),
     ("split", 1, str, "split id (HMDB51 / UCF101)"),
     ("modality", "RGB", str, "RGB | Flow"),
     ("input_channels", 3, int, "3 | 2"),
@@ -77,7 +78,7 @@ _FLAGS = [
     ("clip_grad_norm", 1, int, "1 = clip_grad_norm_(., 18)"),
     ("split_path", "", str, "training list path"),
     ("pb_rate", 4, int, "playback rate of a clip 1,2,4,8"),
-    ("transform_mode", "numpy", str, "transform mode"),
+    ("transform_mode", "numpy", str, "transform mode; --dataset synthetic_video serves img (validation: img_val) and img_test"),
     ("input_size", 320, int, "input size"),
     ("output_feat", 128, int, "output feature size"),
     ("norm_method", "tf_norm", str, "input normalisation"),

@@ -204,3 +204,165 @@ def sample_pair(total_frames: int, frame_w: int, frame_h: int, sample_duration: 
     flip_2 = rng.random() < 0.5
     return PairPlan(ClipPlan(idx_1, ROTATE[r1], box_1, flip_1, use_base_1, base_1),
                     ClipPlan(idx_2, ROTATE[r2], box_2, flip_2, use_base_2, base_2), spa_label, tem_label, pb_label, (r1, r2))
+
+
+# ---- the fine-tune / validation / video-test data path (UcfFineTune, datasets.py:952-1097; transform modes 'img', 'img_val',
+#      'img_test', preprocess_data.py:1131-1149) ------------------------------------------------------------------------------
+FT_MODES = ("img", "img_val", "img_test")
+
+
+@dataclass
+class FtClipPlan:
+    """One fine-tune / validation / test clip: crop ``box`` of the frame -> BICUBIC resize to ``resized`` -> the size x size
+    window at ``window`` of the resized image -> [colour jitter] -> tensor.  'img' crops resize straight to (size, size) with the
+    window at (0, 0); ClipScale -> ClipCenterCrop resizes the whole frame and keeps the centre window."""
+    frames: List[int]                          # 0-based frame indices, in clip order
+    box: Tuple[int, int, int, int]             # (x0, y0, x1, y1) in the frame
+    resized: Tuple[int, int]                   # (width, height) the box is resized to (== the box's size: no resize, ClipScale :853)
+    window: Tuple[int, int]                    # (x, y) origin of the size x size output window in the resized image
+    jitter: Optional[List[Tuple[str, float]]] = None   # ClipColorJitter's operations in shuffled order, or None
+    flip: bool = False                         # 'img' has no flip (preprocess_data.py:1135 is commented out)
+
+
+def _wrap_indices(total_frames: int, sample_duration: int, pb_rate: int, first: int) -> List[int]:
+    index_clip, idx_frame = [], first
+    while len(index_clip) < sample_duration:
+        index_clip.append(idx_frame)
+        idx_frame += pb_rate
+        if idx_frame >= total_frames:
+            idx_frame = first
+    return index_clip
+
+
+def ft_clip_frames(total_frames: int, sample_duration: int, pb_rate: int, rng: random.Random) -> List[int]:
+    """UcfFineTune._get_train_clip / _get_val_clip (datasets.py:1003-1060; validation draws a random start too, :1047): a video
+    longer than clip_range takes ``randint(1, total - clip_range)`` as its 1-based start, a shorter one wraps around from index 0
+    with start_frame = 1 and draws nothing.  0-based indices."""
+    clip_range = (sample_duration - 1) * pb_rate
+    if total_frames - clip_range <= 0:
+        return _wrap_indices(total_frames, sample_duration, pb_rate, 0)          # '%05d.jpg' % (1 + i) -> 0-based i
+    start_frame = rng.randint(1, total_frames - clip_range)
+    return [start_frame - 1 + i for i in range(0, clip_range + 1, pb_rate)]
+
+
+def ft_test_frames(total_frames: int, sample_duration: int, pb_rate: int) -> List[List[int]]:
+    """UcfFineTune._get_test_clip (datasets.py:1062-1097): windows that start at ``arange(1, total - clip_range + 1, clip_range)``
+    plus one extra last window ``arange(total - clip_range, total + 1, pb_rate)``; a short video is sampled once with the
+    1-based wrap-around that never reads frame ``total`` (:1068-1073).  No random draw.  0-based indices per clip."""
+    clip_range = (sample_duration - 1) * pb_rate
+    if total_frames - clip_range <= 0:
+        return [[i - 1 for i in _wrap_indices(total_frames, sample_duration, pb_rate, 1)]]
+    clips = [[s - 1 + j * pb_rate for j in range(sample_duration)] for s in range(1, total_frames - clip_range + 1, clip_range)]
+    clips.append([i - 1 for i in range(total_frames - clip_range, total_frames + 1, pb_rate)])
+    return clips
+
+
+def clip_scale_size(frame_w: int, frame_h: int, size: int) -> Tuple[int, int]:
+    """ClipScale(size) (preprocess_data.py:843-864) -> (width, height): unchanged when the short side already equals ``size``,
+    otherwise the short side becomes ``size`` and the other ``int(size * long / short)``."""
+    if (frame_w <= frame_h and frame_w == size) or (frame_h <= frame_w and frame_h == size):
+        return frame_w, frame_h
+    if frame_w < frame_h:
+        return size, int(size * frame_h / frame_w)
+    return int(size * frame_w / frame_h), size
+
+
+def center_crop_origin(w: int, h: int, size: int) -> Tuple[int, int]:
+    """ClipCenterCrop(size) (preprocess_data.py:815-840): Python's round (half to even): (171 - 112) / 2. -> 30."""
+    return int(round((w - size) / 2.)), int(round((h - size) / 2.))
+
+
+def _scale_center(frames, frame_w, frame_h, short_size, size, jitter=None) -> FtClipPlan:
+    rw, rh = clip_scale_size(frame_w, frame_h, short_size)
+    wx, wy = center_crop_origin(rw, rh, size)
+    if wx < 0 or wy < 0 or wx + size > rw or wy + size > rh:
+        raise ValueError("centre crop %d of the %d x %d scaled frame reaches past it" % (size, rw, rh))
+    return FtClipPlan(frames, (0, 0, frame_w, frame_h), (rw, rh), (wx, wy), jitter)
+
+
+def random_sized_crop(frame_w: int, frame_h: int, rng: random.Random, bottom_area: float = 0.2):
+    """ClipRandomSizedCrop's draws (preprocess_data.py:440-476): the p = 1.0 draw (consumed), then up to 10 attempts of uniform
+    area, uniform aspect, swap draw and -- on success -- randint x, randint y.  -> the box, or None after 10 failures (the caller
+    falls back to ClipScale -> ClipCenterCrop)."""
+    if not rng.random() < 1.0:
+        raise NotImplementedError("p < 1 (plain centre crop) is not on the 'img' path (get_transforms builds p = 1.0)")
+    for _ in range(10):
+        target_area = rng.uniform(bottom_area, 1) * (frame_w * frame_h)
+        aspect_ratio = rng.uniform(3. / 4, 4. / 3)
+        w = int(round(math.sqrt(target_area * aspect_ratio)))
+        h = int(round(math.sqrt(target_area / aspect_ratio)))
+        if rng.random() < 0.5:
+            w, h = h, w
+        if w <= frame_w and h <= frame_h:
+            x1 = rng.randint(0, frame_w - w)
+            y1 = rng.randint(0, frame_h - h)
+            return (x1, y1, x1 + w, y1 + h)
+    return None
+
+
+def colour_jitter_draws(rng: random.Random, p: float, brightness=0.4, contrast=0.4, saturation=0.4, hue=0.1):
+    """ClipColorJitter.__call__ (preprocess_data.py:659-664): one ``random()`` against p, then get_params' four uniforms and the
+    shuffle (:636-654); one transform for the whole clip.  -> [(op, factor)] in applied order, or None."""
+    if not rng.random() < p:
+        return None
+    ops = [("brightness", rng.uniform(max(0, 1 - brightness), 1 + brightness)),
+           ("contrast", rng.uniform(max(0, 1 - contrast), 1 + contrast)),
+           ("saturation", rng.uniform(max(0, 1 - saturation), 1 + saturation)), ("hue", rng.uniform(-hue, hue))]
+    rng.shuffle(ops)
+    return ops
+
+
+def _check_ft_mode(mode: str):
+    if mode in ("numpy", "numpy_val"):
+        raise ValueError("transform mode %r resizes with cv2.resize (preprocess_data.py:867-890); cv2 is not available to pin a "
+                         "bit-exact kernel against, so only the PIL modes %s are served" % (mode, "/".join(FT_MODES)))
+    if mode not in FT_MODES:
+        raise ValueError("transform mode %r: the fine-tune clip path serves %s" % (mode, "/".join(FT_MODES)))
+
+
+def short_side(sample_size: int) -> int:
+    """get_transforms 'img_val' / 'img_test' (preprocess_data.py:1140-1143): 112 -> 128, 224 -> 256."""
+    if sample_size == 112:
+        return 128
+    if sample_size == 224:
+        return 256
+    raise ValueError("sample_size %r: the reference binds short_size only for 112 and 224 (preprocess_data.py:1140-1143) and "
+                     "fails with an unbound name for any other" % (sample_size,))
+
+
+def spatial_plan(mode: str, frames: List[int], frame_w: int, frame_h: int, sample_size: int, rng: Optional[random.Random]):
+    """The transform of one clip, get_transforms(mode) (preprocess_data.py:1131-1149).  'img' draws from ``rng`` (crop, then
+    jitter); 'img_val' / 'img_test' draw nothing."""
+    _check_ft_mode(mode)
+    if mode == "img":
+        box = random_sized_crop(frame_w, frame_h, rng)
+        if box is None:
+            plan = _scale_center(frames, frame_w, frame_h, sample_size, sample_size)       # the fallback :470-473
+        else:
+            plan = FtClipPlan(frames, box, (sample_size, sample_size), (0, 0))
+        plan.jitter = colour_jitter_draws(rng, 0.3)
+        return plan
+    return _scale_center(frames, frame_w, frame_h, short_side(sample_size), sample_size)
+
+
+def sample_ft_clip(total_frames: int, frame_w: int, frame_h: int, sample_duration: int, sample_size: int, pb_rate: int,
+                   mode: str, rng: random.Random) -> FtClipPlan:
+    """One train ('img') or validation ('img_val') sample of UcfFineTune.__getitem__ (datasets.py:993-998): frame indices, then
+    the spatial transform, every draw from ``rng`` in the reference's order."""
+    _check_ft_mode(mode)
+    if mode == "img_test":
+        raise ValueError("'img_test' plans a whole video: use plan_test_video")
+    if mode != "img":
+        short_side(sample_size)                     # refuse before any draw
+    frames = ft_clip_frames(total_frames, sample_duration, pb_rate, rng)
+    return spatial_plan(mode, frames, frame_w, frame_h, sample_size, rng)
+
+
+def plan_test_video(total_frames: int, frame_w: int, frame_h: int, sample_duration: int, sample_size: int, pb_rate: int,
+                    mode: str = "img_test") -> List[FtClipPlan]:
+    """Every clip of one test video (datasets.py:999-1001, 1062-1097) under 'img_test' (or 'img_val'): deterministic."""
+    _check_ft_mode(mode)
+    if mode == "img":
+        raise ValueError("the video test takes 'img_test' (test.py); 'img' is the training augmentation")
+    return [spatial_plan(mode, f, frame_w, frame_h, sample_size, None)
+            for f in ft_test_frames(total_frames, sample_duration, pb_rate)]

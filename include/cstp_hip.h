@@ -377,6 +377,44 @@ int cstp_clip_box_blur(void* stream, uint8_t* img, uint8_t* tmp, int32_t t, int3
                        uint32_t fw, int32_t passes);
 int cstp_clip_finish(void* stream, const uint8_t* src, float* out, int32_t t, int32_t h, int32_t w, int32_t flip);
 
+/* ---- batched, descriptor-driven clip assembly: the fine-tune / validation / video-test data path (reference
+ * data_process/datasets.py:952-1097 UcfFineTune + preprocess_data.py:1131-1149 'img' / 'img_val' / 'img_test') and any other
+ * batch of crop -> BICUBIC resize -> window clips.  One call serves n clips that may come from different videos of different
+ * frame sizes, in TWO launches (horizontal pass, vertical pass) whatever n is.  Per clip: the crop box at (box_x0, box_y0) of
+ * its frames is resized to rw x rh with the caller's coefficient tables (kh / bh of rw entries, kv / bv of rh entries, as
+ * cstp_clip_assemble takes them); only the size x size window at (win_x, win_y) of the resized image is computed, and of the
+ * horizontal pass only the box rows [row_first, row_first + rows) which that window's vertical taps read -- each output pixel
+ * depends on its own taps alone, so the result equals resize-then-crop bit for bit.  Arithmetic as cstp_clip_assemble
+ * (Pillow's 22-bit fixed point, uint8 intermediate, zeros beyond the frame). */
+typedef struct cstp_clip_batch_desc {
+  const uint8_t* frames;   /* this clip's video: uint8 [f][h][w][3] */
+  const int32_t* kh;       /* horizontal coefficients [rw][ksh] */
+  const int32_t* bh;       /* horizontal bounds [rw][2] = (first tap, tap count), relative to the box */
+  const int32_t* kv;       /* vertical coefficients [rh][ksv] */
+  const int32_t* bv;       /* vertical bounds [rh][2] */
+  int64_t tmp_off;         /* this clip's offset (in PIXELS) into the ragged tmp buffer: uint8 [t][rows][size][3] */
+  int32_t f, h, w;         /* its video's frame count and frame size */
+  int32_t idx_off;         /* its t frame indices start here in the shared frame-index array */
+  int32_t box_x0, box_y0;  /* source box origin in the frame (the box may reach past the frame: zeros) */
+  int32_t ksh, ksv;
+  int32_t rw, rh;          /* size of the resized image */
+  int32_t win_x, win_y;    /* output window origin inside the resized image */
+  int32_t row_first, rows; /* box rows the horizontal pass covers */
+  int32_t flip;            /* FLIP_LEFT_RIGHT folded into the fp32 store (ignored for an 8-bit output) */
+  int32_t out_slot;        /* clip index in out (fp32 [slots][3][t][size][size]), or -1 */
+  int32_t out8_slot;       /* clip index in out8 (uint8 [slots8][t][size][size][3], no flip, no normalisation), or -1 */
+  int32_t reserved;        /* 0 */
+} cstp_clip_batch_desc;
+/* sizeof(cstp_clip_batch_desc), for callers that pack the table without this header. */
+size_t cstp_clip_batch_desc_bytes(void);
+/* desc_dev: the n descriptors on the device; desc_host: the same table in host memory, read only during the call to check
+ * every offset and slot against the buffer sizes given here before anything is launched (the device copy may still be in
+ * flight on `stream`).  frame_idx: device int32 [n_idx]; tmp: device uint8, tmp_pixels * 3 bytes; out / out8 may be NULL when
+ * no clip targets them.  Exactly one of out_slot / out8_slot is >= 0 per clip. */
+int cstp_clip_batch_forward(void* stream, const cstp_clip_batch_desc* desc_dev, const cstp_clip_batch_desc* desc_host, int32_t n,
+                            int32_t t, int32_t size, const int32_t* frame_idx, int32_t n_idx, uint8_t* tmp, int64_t tmp_pixels,
+                            float* out, int32_t out_slots, uint8_t* out8, int32_t out8_slots);
+
 /* ---- per-step utilities over FLAT parameter arenas -------------------------------------- */
 /* EMA r21d_byol.py:331-337: target = target*m + online*(1-m) over n floats. */
 int cstp_ema_update(void* stream, float* target, const float* online, size_t n, double m);

@@ -18,7 +18,9 @@ What differs (each a fix of something that cannot work in the reference, none ch
     rejects, r21d_byol.py:400-401); ``--task resume`` continues an ft_all run (undefined model in the reference);
   * the validation loss is averaged over ranks and EVERY rank steps the plateau scheduler (the reference steps it on
     rank 0 only, :278-279, so after the first reduction the ranks train with different learning rates);
-  * --dataset synthetic (class-patterned clips) stands in for the out-of-scope UCF/Kinetics readers.
+  * --dataset synthetic (class-patterned clips) stands in for the out-of-scope UCF/Kinetics readers; --dataset synthetic_video
+    keeps labelled uint8 videos in HBM and runs UcfFineTune's frame selection and the 'img' / 'img_val' transforms on the GPU
+    (cstp_amd.sampler + cstp_clip_batch_forward: a whole batch in two launches) in place of the PIL worker pipeline.
 """
 from __future__ import annotations
 
@@ -53,12 +55,32 @@ def reduce_mean(tensor, world_size):
 
 
 def build_dataset(opts, data_type):
+    if opts.dataset == "synthetic_video":
+        # labelled uint8 videos in HBM; train clips take --transform_mode ('img'), validation '{}_val'.format(mode) (:80,93)
+        from cstp_amd.clip_ops import GpuLabelledVideos
+        mode = opts.transform_mode if data_type == "train" else "{}_val".format(opts.transform_mode)
+        length = opts.synthetic_len if data_type == "train" else max(opts.synthetic_len // 4, 1)
+        return GpuLabelledVideos(torch.device("cuda", opts.device), data_type, mode, n_classes=opts.n_classes,
+                                 sample_duration=opts.sample_duration, sample_size=opts.sample_size, pb_rate=opts.pb_rate,
+                                 length=length, seed=opts.manual_seed)
     if opts.dataset != "synthetic":
-        raise NotImplementedError("dataset %r: only --dataset synthetic is built in (the reference's UCF/Kinetics readers "
-                                  "are outside this package's scope)" % opts.dataset)
+        raise NotImplementedError("dataset %r: only --dataset synthetic and synthetic_video are built in (the reference's "
+                                  "UCF/Kinetics readers are outside this package's scope)" % opts.dataset)
     length = opts.synthetic_len if data_type == "train" else max(opts.synthetic_len // 4, 1)
     return SyntheticLabelledClips(data_type, length, opts.sample_duration, opts.sample_size, opts.n_classes,
                                   opts.manual_seed)
+
+
+def build_dataloader(dataset, opts, data_type):
+    """get_dataloader for the host datasets; the HBM-resident video set brings its own loader (same split of the GLOBAL batch
+    over ranks, same shuffle / drop_last rules) whose batches are assembled on the device."""
+    if opts.dataset == "synthetic_video":
+        from cstp_amd.clip_ops import GpuLabelledLoader
+        world = opts.world_size if opts.distributed else 1
+        loader = GpuLabelledLoader(dataset, max(int(opts.batch_size / world), 1), rank=max(opts.rank, 0) if opts.distributed else 0,
+                                   world_size=world, seed=opts.manual_seed)
+        return loader, (loader if data_type == "train" else None)
+    return get_dataloader(dataset, opts=opts, data_type=data_type)
 
 
 def o_type_for(task):
@@ -167,12 +189,12 @@ def main_worker(local_rank, opts):
     train_data = build_dataset(opts, "train")
     len_train_data = len(train_data)
     print("Length of training data = ", len_train_data)
-    train_dataloader, train_sampler = get_dataloader(train_data, opts=opts, data_type="train")
+    train_dataloader, train_sampler = build_dataloader(train_data, opts, "train")
     print("Preprocessing validation data ...")
     val_data = build_dataset(opts, "val")
     len_val_data = len(val_data)
     print("Length of validation data = ", len_val_data)
-    val_dataloader, _ = get_dataloader(val_data, opts=opts, data_type="val")
+    val_dataloader, _ = build_dataloader(val_data, opts, "val")
 
     print("Loading model... ", opts.model_name, opts.model_depth)
     model, parameters = generate_model(opts)

@@ -9,6 +9,9 @@ Kept: single process / single device, DataLoader(batch_size, shuffle=False) over
 result_path/dataset/t_ft_task (:51-56), generate_model(task 'test') -> strict checkpoint load, model.eval() + no_grad,
 clip logits averaged per video, top-5 from the mean, running top-1 accuracy, one line per video and the final
 "Video accuracy" written to test_{model}{depth}_{dataset}_{split}_{modality}_{T}_plusone.txt (:65-98).
+New: --dataset synthetic_video --transform_mode img_test plans every clip of a video as UcfFineTune._get_test_clip does
+(datasets.py:1062-1097) and assembles them on the device in two launches (cstp_amd.clip_ops.assemble_batch); it also prints the
+clip count of each video.
 """
 from __future__ import annotations
 
@@ -26,8 +29,13 @@ from cstp_amd.utils import AverageMeter
 
 
 def build_dataset(opts):
+    if opts.dataset == "synthetic_video":
+        from cstp_amd.clip_ops import GpuLabelledVideos
+        return GpuLabelledVideos(opts.device, "test", opts.transform_mode, n_classes=opts.n_classes,
+                                 sample_duration=opts.sample_duration, sample_size=opts.sample_size, pb_rate=opts.pb_rate,
+                                 length=max(opts.synthetic_len // 4, 1), seed=opts.manual_seed)
     if opts.dataset != "synthetic":
-        raise NotImplementedError("dataset %r: only --dataset synthetic is built in" % opts.dataset)
+        raise NotImplementedError("dataset %r: only --dataset synthetic and synthetic_video are built in" % opts.dataset)
     return SyntheticLabelledClips("test", max(opts.synthetic_len // 4, 1), opts.sample_duration, opts.sample_size,
                                   opts.n_classes, opts.manual_seed)
 
@@ -51,8 +59,12 @@ def run(opts):
     print("Preprocessing testing data ...")
     test_data = build_dataset(opts)
     print("Length of testing data = ", len(test_data))
-    test_dataloader = DataLoader(test_data, batch_size=1, shuffle=False, num_workers=opts.n_workers, pin_memory=True,
-                                 drop_last=False)
+    if opts.dataset == "synthetic_video":
+        from cstp_amd.clip_ops import GpuLabelledLoader
+        test_dataloader = GpuLabelledLoader(test_data)      # every clip of a video assembled on the device in two launches
+    else:
+        test_dataloader = DataLoader(test_data, batch_size=1, shuffle=False, num_workers=opts.n_workers, pin_memory=True,
+                                     drop_last=False)
     print("Length of test datatloader = ", len(test_dataloader))
     if not opts.test_md_path:
         found = glob.glob(os.path.join(opts.result_path, opts.dataset, opts.t_ft_task, "*_max.pth"))
@@ -72,6 +84,8 @@ def run(opts):
             for i, (inputs, labels) in enumerate(test_dataloader):
                 inputs = torch.squeeze(inputs, 0).to(opts.device, non_blocking=True)
                 labels = labels.to(opts.device, non_blocking=True)
+                if opts.dataset == "synthetic_video":
+                    print("Video[{}]:\tclips = {}".format(i, inputs.shape[0]))
                 _, pred5 = video_prediction(model, inputs, opts.task)
                 acc = float(pred5[0] == int(labels[0]))
                 accuracies.update(acc, 1)
