@@ -186,18 +186,21 @@ def clip_gaussian_blur(clip: torch.Tensor, sigma: float) -> torch.Tensor:
     return out
 
 
-def clip_finish(clip: torch.Tensor, flip: bool) -> torch.Tensor:
-    """[flip] -> ToTensor -> 'tf' normalise: uint8 [T][S][S][3] -> fp32 [3][T][S][S]."""
+def clip_finish(clip: torch.Tensor, flip: bool, out: torch.Tensor = None) -> torch.Tensor:
+    """[flip] -> ToTensor -> 'tf' normalise: uint8 [T][S][S][3] -> fp32 [3][T][S][S] (into ``out``, if given)."""
     clip = _u8_clip(clip)
     t, h, w, _ = clip.shape
-    out = torch.empty((3, t, h, w), dtype=torch.float32, device=clip.device)
+    if out is None:
+        out = torch.empty((3, t, h, w), dtype=torch.float32, device=clip.device)
+    elif out.shape != (3, t, h, w) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != clip.device:
+        raise ValueError("out must be a contiguous fp32 [3, %d, %d, %d] tensor on %s" % (t, h, w, clip.device))
     check(_lib.load().cstp_clip_finish(torch.cuda.current_stream().cuda_stream, clip.data_ptr(), out.data_ptr(), t, h, w,
                                        1 if flip else 0), "cstp_clip_finish")
     return out
 
 
-def apply_base_transform(clip: torch.Tensor, base: "sampler.BasePlan", flip: bool) -> torch.Tensor:
-    """base_transform (preprocess_data.py:1110-1121) on the resized 8-bit clip, in Compose order."""
+def apply_base_transform(clip: torch.Tensor, base: "sampler.BasePlan", flip: bool, out: torch.Tensor = None) -> torch.Tensor:
+    """base_transform (preprocess_data.py:1110-1121) on the resized 8-bit clip, in Compose order (into ``out``, if given)."""
     clip = clip_rotate(clip, base.angle)
     for op, factor in (base.jitter or ()):
         clip = clip_colour(clip, op, factor)
@@ -205,7 +208,7 @@ def apply_base_transform(clip: torch.Tensor, base: "sampler.BasePlan", flip: boo
         clip = clip_gray(clip, base.gray)
     if base.blur_sigma is not None:
         clip = clip_gaussian_blur(clip, base.blur_sigma)
-    return clip_finish(clip, flip)
+    return clip_finish(clip, flip, out)
 
 
 def assemble_clip(frames: torch.Tensor, plan: "sampler.ClipPlan", size: int) -> torch.Tensor:
@@ -321,7 +324,7 @@ class GpuClipLoader:
 # struct cstp_clip_batch_desc (include/cstp_hip.h), packed by hand into the pinned upload buffer
 _BATCH_DESC = np.dtype([(n, "<u8") for n in ("frames", "kh", "bh", "kv", "bv")] + [("tmp_off", "<i8")]
                        + [(n, "<i4") for n in ("f", "h", "w", "idx_off", "box_x0", "box_y0", "ksh", "ksv", "rw", "rh", "win_x",
-                                               "win_y", "row_first", "rows", "flip", "out_slot", "out8_slot", "reserved")])
+                                               "win_y", "row_first", "rows", "flip", "out_slot", "out8_slot", "rot")])
 
 
 def window_rows(in_size: int, out_size: int, origin: int, size: int):
@@ -338,11 +341,33 @@ def assemble_batch(videos, plans, size: int, out: torch.Tensor = None) -> torch.
     may come from videos of different frame sizes.  Descriptors and frame indices travel in ONE pinned upload; nothing is
     allocated per clip.  Clips with colour jitter leave the resize as 8-bit frames and go on through cstp_clip_blend / _hue /
     _finish, one transform per clip (ClipColorJitter)."""
-    lib = _lib.load()
     plans = list(plans)
-    n = len(plans)
-    if n == 0:
+    if len(plans) == 0:
         raise ValueError("assemble_batch needs at least one plan")
+    for p in plans:
+        if getattr(p, "rotate", 0) or getattr(p, "base", None) is not None:
+            raise ValueError("assemble_batch serves crop / scale / window / jitter plans; rotated and base_transform clips go "
+                             "through assemble_clip")
+    jittered = [i for i, p in enumerate(plans) if getattr(p, "jitter", None)]
+    out, u8 = _batch_forward(videos, plans, size, out, jittered)
+    lib, st = _lib.load(), torch.cuda.current_stream().cuda_stream
+    t = len(plans[0].frames)
+    for j, i in enumerate(jittered):
+        clip = u8[j]
+        for op, factor in plans[i].jitter:
+            clip = clip_colour(clip, op, factor)
+        check(lib.cstp_clip_finish(st, clip.data_ptr(), out[i].data_ptr(), t, size, size, 1 if getattr(plans[i], "flip", False) else 0),
+              "cstp_clip_finish")
+    return out
+
+
+def _batch_forward(videos, plans, size: int, out, eight_bit):
+    """The descriptor table, its one pinned upload and the two launches of cstp_clip_batch_forward for ``plans`` (any mix of
+    FtClipPlan / ClipPlan: ``rotate`` is honoured here).  The clips listed in ``eight_bit`` stop after the resize as uint8
+    [t][size][size][3] (no flip, no normalisation) for the caller's 8-bit operations; every other clip i is finished into
+    out[i].  -> (out fp32 [n][3][t][size][size], u8 [len(eight_bit)][t][size][size][3] or None)."""
+    lib = _lib.load()
+    n = len(plans)
     if torch.is_tensor(videos):
         videos = [videos] * n
     if len(videos) != n:
@@ -352,8 +377,7 @@ def assemble_batch(videos, plans, size: int, out: torch.Tensor = None) -> torch.
                              % (lib.cstp_clip_batch_desc_bytes(), _BATCH_DESC.itemsize))
     dev = videos[0].device
     t = len(plans[0].frames)
-    jittered = [i for i, p in enumerate(plans) if getattr(p, "jitter", None)]
-    slot8 = {i: j for j, i in enumerate(jittered)}
+    slot8 = {i: j for j, i in enumerate(eight_bit)}
     nbytes = n * _BATCH_DESC.itemsize + 4 * n * t
     host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
     view = host.numpy()
@@ -365,9 +389,9 @@ def assemble_batch(videos, plans, size: int, out: torch.Tensor = None) -> torch.
             raise _lib.CstpError("videos must be contiguous uint8 [F, H, W, 3] tensors on one HIP device (cstp_amd has no CPU path)")
         if len(p.frames) != t:
             raise ValueError("clips of %d and %d frames in one batch" % (t, len(p.frames)))
-        if getattr(p, "rotate", 0) or getattr(p, "base", None) is not None:
-            raise ValueError("assemble_batch serves crop / scale / window / jitter plans; rotated and base_transform clips go "
-                             "through assemble_clip")
+        rot = int(getattr(p, "rotate", 0))
+        if rot not in (0, 90, 180, 270):
+            raise ValueError("rotation %r: a clip is rotated by 0 / 90 / 180 / 270 degrees" % (rot,))
         x0, y0, x1, y1 = p.box
         if not (x0 < x1 and y0 < y1):
             raise _lib.CstpError("empty crop box %s" % (p.box,))
@@ -381,7 +405,7 @@ def assemble_batch(videos, plans, size: int, out: torch.Tensor = None) -> torch.
         f, h, w, _ = v.shape
         desc[i] = (v.data_ptr(), kh.data_ptr(), bh.data_ptr(), kv.data_ptr(), bv.data_ptr(), tmp_pixels, f, h, w, i * t, x0, y0,
                    ksh, ksv, rw, rh, wx, wy, first, rows, 1 if getattr(p, "flip", False) else 0,
-                   -1 if i in slot8 else i, slot8.get(i, -1), 0)
+                   -1 if i in slot8 else i, slot8.get(i, -1), rot)
         idx[i * t:(i + 1) * t] = p.frames
         tmp_pixels += t * rows * size
     if out is None:
@@ -391,19 +415,41 @@ def assemble_batch(videos, plans, size: int, out: torch.Tensor = None) -> torch.
     table = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     table.copy_(host, non_blocking=True)
     tmp = torch.empty(tmp_pixels * 3, dtype=torch.uint8, device=dev)
-    u8 = torch.empty((len(jittered), t, size, size, 3), dtype=torch.uint8, device=dev) if jittered else None
+    u8 = torch.empty((len(slot8), t, size, size, 3), dtype=torch.uint8, device=dev) if slot8 else None
     st = torch.cuda.current_stream().cuda_stream
     check(lib.cstp_clip_batch_forward(st, table.data_ptr(), host.data_ptr(), n, t, size,
                                       table.data_ptr() + n * _BATCH_DESC.itemsize, n * t, tmp.data_ptr(), tmp_pixels,
-                                      out.data_ptr(), n, None if u8 is None else u8.data_ptr(), len(jittered)),
+                                      out.data_ptr(), n, None if u8 is None else u8.data_ptr(), len(slot8)),
           "cstp_clip_batch_forward")
-    for i in jittered:
-        clip = u8[slot8[i]]
-        for op, factor in plans[i].jitter:
-            clip = clip_colour(clip, op, factor)
-        check(lib.cstp_clip_finish(st, clip.data_ptr(), out[i].data_ptr(), t, size, size, 1 if getattr(plans[i], "flip", False) else 0),
-              "cstp_clip_finish")
-    return out
+    return out, u8
+
+
+def assemble_pairs(videos, pair_plans, size: int, out: torch.Tensor = None):
+    """A whole batch of pre-training pairs: pair_plans[i] (``sampler.PairPlan``) cut from videos[i] (uint8 [F][H][W][3]; a single
+    tensor serves every pair) -> (clip_1 [B][3][T][size][size], clip_2 likewise), the two halves of one fp32 [2][B][3][T][size][size]
+    tensor (``out``, if given).  2B descriptors -- rotation codes, boxes that may reach past the rotated frame, flips -- travel in
+    ONE pinned upload and are served by the two launches of cstp_clip_batch_forward.  ``null_transform`` clips are written straight
+    into their slot; ``base_transform`` clips leave the resize as 8-bit frames and go on through ``apply_base_transform`` into
+    theirs.  Bit-identical to ``assemble_clip`` on every clip."""
+    pair_plans = list(pair_plans)
+    b = len(pair_plans)
+    if b == 0:
+        raise ValueError("assemble_pairs needs at least one pair")
+    if torch.is_tensor(videos):
+        videos = [videos] * b
+    if len(videos) != b:
+        raise ValueError("%d videos for %d pairs" % (len(videos), b))
+    plans = [p.clip_1 for p in pair_plans] + [p.clip_2 for p in pair_plans]
+    t = len(plans[0].frames)
+    if out is not None:
+        if out.shape != (2, b, 3, t, size, size):
+            raise ValueError("out must be a contiguous fp32 [2, %d, 3, %d, %d, %d] tensor" % (b, t, size, size))
+        out = out.view(2 * b, 3, t, size, size)
+    based = [i for i, p in enumerate(plans) if p.base is not None]
+    flat, u8 = _batch_forward(list(videos) * 2, plans, size, out, based)
+    for j, i in enumerate(based):
+        apply_base_transform(u8[j], plans[i].base, plans[i].flip, out=flat[i])
+    return flat[:b], flat[b:]
 
 
 def _labelled_video(label: int, n_classes: int, frames: int, height: int, width: int, gen, device) -> torch.Tensor:

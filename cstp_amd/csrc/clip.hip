@@ -12,6 +12,7 @@
 // 240x320 frames: 3.7 MB in, 2.4 MB out).
 // The fine-tune / validation / video-test clips (datasets.py:952-1097 UcfFineTune, preprocess_data.py:1131-1149) come a BATCH at a
 // time through cstp_clip_batch_forward at the end of this file: one descriptor table, two launches for any number of clips.
+// A batch of pre-training pairs takes the same road, with a rotation code per clip (clip_ops.assemble_pairs).
 #include "common.h"
 
 namespace cstp {
@@ -388,7 +389,7 @@ extern "C" int cstp_clip_finish(void* stream, const uint8_t* src, float* out, in
 // ---- batched, descriptor-driven assembly (cstp_clip_batch_forward): the fine-tune / validation / video-test data path -------
 // A whole batch -- clips of different videos, frame sizes, boxes and scales -- in two launches: blockIdx.y picks the clip's
 // descriptor, blockIdx.x strides over that clip's pixels.  The arithmetic is that of clip_resize_h_kernel / clip_resize_v_kernel
-// (no rotation on this path); new is the output WINDOW: of the resized rw x rh image only the size x size window at
+// (rotation included: desc.rot, see below); new is the output WINDOW: of the resized rw x rh image only the size x size window at
 // (win_x, win_y) is produced, so ClipScale -> ClipCenterCrop (240x320 -> 128x170 -> 112x112) computes 112 of 170 columns and
 // only the tmp rows the window's vertical taps read, and the result still equals resize-then-crop bit for bit because an output
 // pixel depends on its own taps alone.
@@ -398,6 +399,15 @@ extern "C" int cstp_clip_finish(void* stream, const uint8_t* src, float* out, in
 // lanes of a wave read neighbouring output columns, whose tap spans overlap, and the vertical pass reads tmp rows that 64 lanes
 // share coalesced.  Tables (at most a few KiB per axis) and descriptors stay in the scalar / L2 caches.  Next to a training step
 // the two launches are noise; what the batching removes is the 2+ launches, the blocking index upload and the allocation PER CLIP.
+// Rotation (desc.rot, the pre-training pairs): each tap is mapped to the stored frame as clip_resize_h_kernel maps it; rot == 0
+// takes the branch it always took.  Under 180 a wave still reads one stored row, backwards.  Under 90 / 270 the roles of the
+// axes swap: the taps of ONE output pixel walk a column of the stored frame (stride w * 3 bytes, a new 128-byte line per tap),
+// and the 64 lanes of a wave -- neighbouring output columns of one row -- read 64 different stored rows at one stored column,
+// so a wave's tap load touches up to 64 lines instead of the 2..6 of the row walk.  The lines are not wasted: the output rows
+// y + 1 .. y + 42 (128 / 3 pixels) of the same frame read the same lines at the neighbouring stored columns, and those rows
+// belong to the next waves of the same or the next block, so the reuse is served by the L2 (a 240x320 frame is 230 KB).
+// No measured change followed from this yet: the by-rotation line of tools/bench_frames.py has not been run on a GPU, and no
+// tiling (a transposing LDS stage for 90 / 270) is attempted before it shows that the column walk costs time worth having.
 namespace cstp {
 
 __global__ void __launch_bounds__(256) clip_batch_h_kernel(const cstp_clip_batch_desc* __restrict__ descs,
@@ -416,9 +426,23 @@ __global__ void __launch_bounds__(256) clip_batch_h_kernel(const cstp_clip_batch
     const int x0 = d.bh[2 * cx];
     int n = d.bh[2 * cx + 1];
     n = n > d.ksh ? d.ksh : n;
-    const int oy = d.box_y0 + d.row_first + y;             // row in the frame
+    const int oy = d.box_y0 + d.row_first + y;             // row in the (rotated) frame
     int a0 = 1 << (CLIP_PRECISION_BITS - 1), a1 = a0, a2 = a0;
-    if (oy >= 0 && oy < d.h) {                             // Image.crop beyond the frame reads black (0, 0, 0)
+    if (d.rot != 0) {                                      // uniform over the block: one descriptor per blockIdx.y
+      const uint8_t* fp = d.frames + (size_t)f * d.h * d.w * 3;
+      const int32_t* k = d.kh + (size_t)cx * d.ksh;
+      for (int j = 0; j < n; ++j) {
+        const int rx = d.box_x0 + x0 + j;                  // column in the rotated frame
+        int sx, sy;                                        // the same pixel in the stored frame (inverse of Image.transpose)
+        if (d.rot == 90) { sx = d.w - 1 - oy; sy = rx; }
+        else if (d.rot == 180) { sx = d.w - 1 - rx; sy = d.h - 1 - oy; }
+        else { sx = oy; sy = d.h - 1 - rx; }               // 270
+        if (sx < 0 || sx >= d.w || sy < 0 || sy >= d.h) continue;   // Image.crop beyond the rotated frame reads black
+        const uint8_t* p = fp + ((size_t)sy * d.w + sx) * 3;
+        const int kj = k[j];
+        a0 += (int)p[0] * kj; a1 += (int)p[1] * kj; a2 += (int)p[2] * kj;
+      }
+    } else if (oy >= 0 && oy < d.h) {                      // Image.crop beyond the frame reads black (0, 0, 0)
       const uint8_t* row = d.frames + ((size_t)f * d.h + oy) * d.w * 3;
       const int32_t* k = d.kh + (size_t)cx * d.ksh;
       for (int j = 0; j < n; ++j) {
@@ -491,6 +515,7 @@ extern "C" int cstp_clip_batch_forward(void* stream, const cstp_clip_batch_desc*
     const cstp_clip_batch_desc& d = desc_host[i];
     CSTP_REQUIRE(d.frames && d.kh && d.bh && d.kv && d.bv, "null pointer in a descriptor");
     CSTP_REQUIRE(d.f > 0 && d.h > 0 && d.w > 0 && d.h < 32768 && d.w < 32768, "bad frame shape in a descriptor");
+    CSTP_REQUIRE(d.rot == 0 || d.rot == 90 || d.rot == 180 || d.rot == 270, "rotation of a descriptor must be 0 / 90 / 180 / 270");
     CSTP_REQUIRE(d.idx_off >= 0 && (int64_t)d.idx_off + t <= n_idx, "frame indices of a descriptor leave the index array");
     CSTP_REQUIRE(d.ksh > 0 && d.ksv > 0 && d.rw > 0 && d.rh > 0, "bad table shape in a descriptor");
     CSTP_REQUIRE(d.win_x >= 0 && d.win_y >= 0 && (int64_t)d.win_x + size <= d.rw && (int64_t)d.win_y + size <= d.rh,

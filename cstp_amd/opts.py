@@ -20,11 +20,14 @@ import os
 # (flag, default, type, help) -- type None means store_true
 _FLAGS = [
     # datasets
-    ("frame_dir", "dataset/HMDB51/", str, "path of jpg files"),
-    ("annotation_path", "dataset/HMDB51_labels", str, "label paths"),
-    ("dataset", "HMDB51", str, "HMDB51 | UCF101 | Kinetics | synthetic | synthetic_video (HBM-resident videos, clips assembled on the GPU: "
-     "pre-training, fine-tuning with --transform_mode img, video test with --transform_mode img_test)"),
-    ("split", 1, str, "split id (HMDB51 / UCF101)"),
+    ("frame_dir", "dataset/HMDB51/", str, "root of the frame folders: <frame_dir>/<Class>/<v_name>/%05d.jpg, 1-based"),
+    ("annotation_path", "dataset/HMDB51_labels", str, "folder of trainlist0{split}_nframe.txt / testlist0{split}_nframe.txt "
+     "(lines 'Class/v_name.avi <label> <n_frames>')"),
+    ("dataset", "HMDB51", str, "UcfRepreBYOLSpPre (main_byol.py) | UcfFineTune (main_ft_mp.py, test.py): UCF-style frame folders, JPEGs "
+     "decoded on --n_workers CPU threads, clips assembled on the GPU | synthetic | synthetic_video (HBM-resident videos, clips "
+     "assembled on the GPU: pre-training, fine-tuning with --transform_mode img, video test with --transform_mode img_test); "
+     "the LMDB / Kinetics names are refused"),
+    ("split", 1, str, "split id (HMDB51 / UCF101): picks trainlist0{split}_nframe.txt / testlist0{split}_nframe.txt"),
     ("modality", "RGB", str, "RGB | Flow"),
     ("input_channels", 3, int, "3 | 2"),
     ("n_classes", 400, int, "number of classes"),
@@ -39,7 +42,7 @@ _FLAGS = [
     ("sample_size", 112, int, "clip height and width"),
     ("sample_duration", 16, int, "clip length in frames"),
     ("batch_size", 32, int, "GLOBAL batch size (split over ranks)"),
-    ("n_workers", 4, int, "dataloader workers"),
+    ("n_workers", 4, int, "dataloader workers; for the frame-folder data sets the JPEG decode threads (at least 1, at most 16)"),
     ("pretrained_path", "", str, "pretrained checkpoint"),
     ("test_md_path", "", str, "checkpoint to test"),
     ("resume_md_path", "", str, "checkpoint to resume"),
@@ -78,7 +81,7 @@ _FLAGS = [
     ("clip_grad_norm", 1, int, "1 = clip_grad_norm_(., 18)"),
     ("split_path", "", str, "training list path"),
     ("pb_rate", 4, int, "playback rate of a clip 1,2,4,8"),
-    ("transform_mode", "numpy", str, "transform mode; --dataset synthetic_video serves img (validation: img_val) and img_test"),
+    ("transform_mode", "numpy", str, "transform mode; --dataset synthetic_video and UcfFineTune serve img (validation: img_val) and img_test"),
     ("input_size", 320, int, "input size"),
     ("output_feat", 128, int, "output feature size"),
     ("norm_method", "tf_norm", str, "input normalisation"),

@@ -385,7 +385,9 @@ int cstp_clip_finish(void* stream, const uint8_t* src, float* out, int32_t t, in
  * cstp_clip_assemble takes them); only the size x size window at (win_x, win_y) of the resized image is computed, and of the
  * horizontal pass only the box rows [row_first, row_first + rows) which that window's vertical taps read -- each output pixel
  * depends on its own taps alone, so the result equals resize-then-crop bit for bit.  Arithmetic as cstp_clip_assemble
- * (Pillow's 22-bit fixed point, uint8 intermediate, zeros beyond the frame). */
+ * (Pillow's 22-bit fixed point, uint8 intermediate, zeros beyond the frame).  A clip may carry a rotation by a multiple of 90
+ * degrees (the pre-training pairs, datasets.py:876-948), folded into the source indexing of the horizontal pass exactly as
+ * cstp_clip_assemble folds it. */
 typedef struct cstp_clip_batch_desc {
   const uint8_t* frames;   /* this clip's video: uint8 [f][h][w][3] */
   const int32_t* kh;       /* horizontal coefficients [rw][ksh] */
@@ -403,7 +405,8 @@ typedef struct cstp_clip_batch_desc {
   int32_t flip;            /* FLIP_LEFT_RIGHT folded into the fp32 store (ignored for an 8-bit output) */
   int32_t out_slot;        /* clip index in out (fp32 [slots][3][t][size][size]), or -1 */
   int32_t out8_slot;       /* clip index in out8 (uint8 [slots8][t][size][size][3], no flip, no normalisation), or -1 */
-  int32_t reserved;        /* 0 */
+  int32_t rot;             /* 0 / 90 / 180 / 270: Image.transpose(ROTATE_*) of the whole frame before the crop; box_x0 / box_y0 and
+                              the zeros beyond the frame then refer to the ROTATED frame (h x w pixels for 90 / 270) */
 } cstp_clip_batch_desc;
 /* sizeof(cstp_clip_batch_desc), for callers that pack the table without this header. */
 size_t cstp_clip_batch_desc_bytes(void);

@@ -16,8 +16,9 @@ and optimiser step (:60-91), the per-iteration print columns (:96-117), the per-
 (:119-130) and the save_{epoch}.pth checkpoint dict every 100 epochs (:132-140).
 What differs: --dataset synthetic feeds random clips through a DataLoader; --dataset synthetic_video keeps decoded
 uint8 videos in HBM and samples / rotates / crops / resizes / flips / normalises the clip pairs on the GPU
-(cstp_amd.sampler + cstp_clip_assemble) in place of the reference's PIL worker pipeline; reading JPEG / LMDB data
-sets is out of scope; the log scalars reach the host through one pinned-memory copy per iteration, read one step late
+(cstp_amd.sampler + cstp_clip_assemble) in place of the reference's PIL worker pipeline; --dataset UcfRepreBYOLSpPre
+reads UCF-style frame folders (--frame_dir, --annotation_path, --split; --n_workers decode threads) and runs everything
+after the JPEG decode on the GPU (cstp_amd.frame_folder); the LMDB data sets are out of scope; the log scalars reach the host through one pinned-memory copy per iteration, read one step late
 (cstp_amd.train.LaggedScalars), instead of seven .item() syncs and a blocking all-reduce per iteration.
 """
 from __future__ import annotations
@@ -48,9 +49,14 @@ def build_dataset(opts):
         from cstp_amd.clip_ops import GpuVideoClips
         return GpuVideoClips(torch.device("cuda", opts.local_rank), sample_duration=opts.sample_duration,
                              sample_size=opts.sample_size, length=opts.synthetic_len, seed=opts.manual_seed)
+    if opts.dataset == "UcfRepreBYOLSpPre":
+        # frame folders listed under --annotation_path: JPEGs decoded on CPU threads, everything after the decode on the GPU
+        from cstp_amd.frame_folder import build_pretrain
+        return build_pretrain(opts, torch.device("cuda", opts.local_rank))
     if opts.dataset != "synthetic":
-        raise NotImplementedError("dataset %r: --dataset synthetic and synthetic_video are built in (reading the reference's "
-                                  "JPEG / LMDB data sets is outside this package's scope)" % opts.dataset)
+        raise NotImplementedError("dataset %r: --dataset synthetic, synthetic_video and UcfRepreBYOLSpPre (UCF-style frame "
+                                  "folders) are built in; the reference's LMDB data sets are outside this package's scope"
+                                  % opts.dataset)
     return SyntheticClips(opts.synthetic_len, opts.sample_duration, opts.sample_size, opts.manual_seed)
 
 
@@ -130,6 +136,10 @@ def main_worker(local_rank, opts):
         from cstp_amd.clip_ops import GpuClipLoader
         loader = sampler = GpuClipLoader(train_data, per_rank, rank=max(opts.rank, 0), world_size=opts.world_size,
                                          seed=opts.manual_seed)
+    elif opts.dataset == "UcfRepreBYOLSpPre":
+        from cstp_amd.frame_folder import FramePairLoader
+        loader = sampler = FramePairLoader(train_data, per_rank, rank=max(opts.rank, 0), world_size=opts.world_size,
+                                           seed=opts.manual_seed)
     else:
         sampler = DistributedSampler(train_data, num_replicas=opts.world_size, rank=max(opts.rank, 0), shuffle=True) \
             if opts.distributed else None

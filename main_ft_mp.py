@@ -20,7 +20,9 @@ What differs (each a fix of something that cannot work in the reference, none ch
     rank 0 only, :278-279, so after the first reduction the ranks train with different learning rates);
   * --dataset synthetic (class-patterned clips) stands in for the out-of-scope UCF/Kinetics readers; --dataset synthetic_video
     keeps labelled uint8 videos in HBM and runs UcfFineTune's frame selection and the 'img' / 'img_val' transforms on the GPU
-    (cstp_amd.sampler + cstp_clip_batch_forward: a whole batch in two launches) in place of the PIL worker pipeline.
+    (cstp_amd.sampler + cstp_clip_batch_forward: a whole batch in two launches) in place of the PIL worker pipeline;
+    --dataset UcfFineTune feeds the same path from UCF-style frame folders (--frame_dir, --annotation_path, --split;
+    --n_workers JPEG decode threads; cstp_amd.frame_folder).
 """
 from __future__ import annotations
 
@@ -63,9 +65,15 @@ def build_dataset(opts, data_type):
         return GpuLabelledVideos(torch.device("cuda", opts.device), data_type, mode, n_classes=opts.n_classes,
                                  sample_duration=opts.sample_duration, sample_size=opts.sample_size, pb_rate=opts.pb_rate,
                                  length=length, seed=opts.manual_seed)
+    if opts.dataset == "UcfFineTune":
+        # frame folders listed under --annotation_path; the same modes, the JPEGs decoded on CPU threads
+        from cstp_amd.frame_folder import build_finetune
+        mode = opts.transform_mode if data_type == "train" else "{}_val".format(opts.transform_mode)
+        return build_finetune(opts, torch.device("cuda", opts.device), data_type, mode)
     if opts.dataset != "synthetic":
-        raise NotImplementedError("dataset %r: only --dataset synthetic and synthetic_video are built in (the reference's "
-                                  "UCF/Kinetics readers are outside this package's scope)" % opts.dataset)
+        raise NotImplementedError("dataset %r: --dataset synthetic, synthetic_video and UcfFineTune (UCF-style frame folders) are "
+                                  "built in (the reference's Kinetics / LMDB readers are outside this package's scope)"
+                                  % opts.dataset)
     length = opts.synthetic_len if data_type == "train" else max(opts.synthetic_len // 4, 1)
     return SyntheticLabelledClips(data_type, length, opts.sample_duration, opts.sample_size, opts.n_classes,
                                   opts.manual_seed)
@@ -74,8 +82,10 @@ def build_dataset(opts, data_type):
 def build_dataloader(dataset, opts, data_type):
     """get_dataloader for the host datasets; the HBM-resident video set brings its own loader (same split of the GLOBAL batch
     over ranks, same shuffle / drop_last rules) whose batches are assembled on the device."""
-    if opts.dataset == "synthetic_video":
+    if opts.dataset in ("synthetic_video", "UcfFineTune"):
         from cstp_amd.clip_ops import GpuLabelledLoader
+        if opts.dataset == "UcfFineTune":
+            from cstp_amd.frame_folder import FrameLabelledLoader as GpuLabelledLoader      # + the decode prefetch
         world = opts.world_size if opts.distributed else 1
         loader = GpuLabelledLoader(dataset, max(int(opts.batch_size / world), 1), rank=max(opts.rank, 0) if opts.distributed else 0,
                                    world_size=world, seed=opts.manual_seed)

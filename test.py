@@ -11,7 +11,7 @@ clip logits averaged per video, top-5 from the mean, running top-1 accuracy, one
 "Video accuracy" written to test_{model}{depth}_{dataset}_{split}_{modality}_{T}_plusone.txt (:65-98).
 New: --dataset synthetic_video --transform_mode img_test plans every clip of a video as UcfFineTune._get_test_clip does
 (datasets.py:1062-1097) and assembles them on the device in two launches (cstp_amd.clip_ops.assemble_batch); it also prints the
-clip count of each video.
+clip count of each video; --dataset UcfFineTune does the same from UCF-style frame folders (cstp_amd.frame_folder).
 """
 from __future__ import annotations
 
@@ -34,8 +34,11 @@ def build_dataset(opts):
         return GpuLabelledVideos(opts.device, "test", opts.transform_mode, n_classes=opts.n_classes,
                                  sample_duration=opts.sample_duration, sample_size=opts.sample_size, pb_rate=opts.pb_rate,
                                  length=max(opts.synthetic_len // 4, 1), seed=opts.manual_seed)
+    if opts.dataset == "UcfFineTune":
+        from cstp_amd.frame_folder import build_finetune
+        return build_finetune(opts, opts.device, "test", opts.transform_mode)
     if opts.dataset != "synthetic":
-        raise NotImplementedError("dataset %r: only --dataset synthetic and synthetic_video are built in" % opts.dataset)
+        raise NotImplementedError("dataset %r: only --dataset synthetic, synthetic_video and UcfFineTune are built in" % opts.dataset)
     return SyntheticLabelledClips("test", max(opts.synthetic_len // 4, 1), opts.sample_duration, opts.sample_size,
                                   opts.n_classes, opts.manual_seed)
 
@@ -62,6 +65,9 @@ def run(opts):
     if opts.dataset == "synthetic_video":
         from cstp_amd.clip_ops import GpuLabelledLoader
         test_dataloader = GpuLabelledLoader(test_data)      # every clip of a video assembled on the device in two launches
+    elif opts.dataset == "UcfFineTune":
+        from cstp_amd.frame_folder import FrameLabelledLoader
+        test_dataloader = FrameLabelledLoader(test_data)    # the same, the next video's frames decoded meanwhile
     else:
         test_dataloader = DataLoader(test_data, batch_size=1, shuffle=False, num_workers=opts.n_workers, pin_memory=True,
                                      drop_last=False)
@@ -84,7 +90,7 @@ def run(opts):
             for i, (inputs, labels) in enumerate(test_dataloader):
                 inputs = torch.squeeze(inputs, 0).to(opts.device, non_blocking=True)
                 labels = labels.to(opts.device, non_blocking=True)
-                if opts.dataset == "synthetic_video":
+                if opts.dataset in ("synthetic_video", "UcfFineTune"):
                     print("Video[{}]:\tclips = {}".format(i, inputs.shape[0]))
                 _, pred5 = video_prediction(model, inputs, opts.task)
                 acc = float(pred5[0] == int(labels[0]))
