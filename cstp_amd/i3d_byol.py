@@ -35,7 +35,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .r21d_byol import OVERLAP_TARGET_FORWARD, BatchNorm1d, BatchNorm3d, ByolBase, Conv3d, Linear, Predictor
+from .r21d_byol import BatchNorm1d, BatchNorm3d, ByolBase, Conv3d, Linear, Predictor
 
 # A/B switch (read at import): 0 = SAME pooling and the Mixed tail composed from ATen + the per-branch ops
 FUSED = os.environ.get("CSTP_I3D_FUSED", "1") != "0"
@@ -279,15 +279,15 @@ class I3D(nn.Module):
                 raise ValueError("clip %s: the I3D classifier squeezes a 1x1 spatial map, i.e. a final map of exactly 7x7 "
                                  "(194..225 pixels); got %s" % (tuple(shape[1:]), fm))
 
-    def forward(self, x, groups=1, after_stem=None):
+    def forward(self, x, groups=1, after_early_stage=None):
         """``groups`` > 1: x holds that many independent forward calls back to back along the batch axis (per-call BN
-        statistics).  ``after_stem``: called once conv3d_2c_3x3 is enqueued (I3DBYOL starts the target network's stream there)."""
+        statistics).  ``after_early_stage``: called once conv3d_2c_3x3 is enqueued (I3DBYOL starts the target network's stream there)."""
         self.check_clip(x.shape)
         x = self.conv3d_1a_7x7(x, groups)
         x = self.maxPool3d_2a_3x3(x)
         x = self.conv3d_2c_3x3(self.conv3d_2b_1x1(x, groups), groups)
-        if after_stem is not None:
-            after_stem()
+        if after_early_stage is not None:
+            after_early_stage()
         x = self.maxPool3d_3a_3x3(x)
         x = self.mixed_3c(self.mixed_3b(x, groups), groups)
         x = self.maxPool3d_4a_3x3(x)
@@ -304,6 +304,7 @@ class I3D(nn.Module):
 class I3DBYOL(ByolBase):
     """forward(x1, x2, o_type='loss_com') -> (loss_byol, (pred_spa, pred_tem, pred_pb_1, pred_pb_2, pred_rot_1, pred_rot_2))
     with [B,5], [B,5], [B,4] x4 logits (i3d_byol.py:748-772)."""
+    ROT_HEAD = "rot_cls"      # the rotation head's attribute name in this wrapper
 
     def __init__(self, momentum=0.996, pretrain=True, opts=None):
         super().__init__()
@@ -332,52 +333,7 @@ class I3DBYOL(ByolBase):
 
     def forward(self, x1, x2=None, o_type="r_byol"):
         if o_type == "loss_com":
-            if not self.pretrain:
-                raise AttributeError("I3DBYOL(pretrain=False) has no target_net/predictor: o_type='loss_com' needs pretrain=True")
-            if x2 is None or x2.shape != x1.shape:
-                raise ValueError("o_type='loss_com' needs two clips of identical shape")
-            b = x1.shape[0]
-            x = torch.cat((x1, x2), dim=0)     # both views through one launch sequence, per-view BN statistics (groups=2)
-            if OVERLAP_TARGET_FORWARD and x.is_cuda:
-                # target forward on a second HIP stream, staggered behind the online stem (see R21DBYOL.forward)
-                main = torch.cuda.current_stream(x.device)
-                side = self._side_stream(x.device)
-                tgt = {}
-
-                def start_target():
-                    side.wait_stream(main)
-                    with torch.cuda.stream(side), torch.no_grad():
-                        self._update_target_net()             # EMA BEFORE the target forward (:754)
-                        target_feat = self.target_net(x, groups=2)
-                        tgt["swapped"] = torch.cat((target_feat[b:], target_feat[:b]), dim=0).detach()
-
-                online_feat = self.online_net(x, groups=2, after_stem=start_target)
-                online_pred = self.predictor(online_feat, groups=2)
-                main.wait_stream(side)
-                target_swapped = tgt["swapped"]
-                target_swapped.record_stream(main)
-                x.record_stream(side)
-            else:
-                online_feat = self.online_net(x, groups=2)
-                online_pred = self.predictor(online_feat, groups=2)
-                with torch.no_grad():
-                    self._update_target_net()                     # EMA BEFORE the target forward (:754)
-                    target_feat = self.target_net(x, groups=2)
-                    target_swapped = torch.cat((target_feat[b:], target_feat[:b]), dim=0).detach()
-            rows = self._loss_fn(online_pred, target_swapped)   # loss_fn(pred_1, t_2) + loss_fn(t_1, pred_2)  (:682-686)
-            loss = rows[:b] + rows[b:]
-            feat_cat = torch.cat((online_feat[:b], online_feat[b:]), dim=1)
-            pred_spa = self.overlap_spa(feat_cat)
-            pred_tem = self.overlap_tem(feat_cat)
-            pred_pb = self.pb_cls(online_feat)
-            pred_rot = self.rot_cls(online_feat)
-            if self._arenas is not None:
-                nbt = self._arenas["nbt"]
-                nbt["online"] += 2
-                nbt["target"] += 2
-                nbt["heads"] += nbt["heads_inc"]
-            self.last_projections = (online_feat[:b], online_feat[b:])   # NT-Xent head input (no projector in this wrapper)
-            return loss.mean(), (pred_spa, pred_tem, pred_pb[:b], pred_pb[b:], pred_rot[:b], pred_rot[b:])
+            return self._two_view_step(x1, x2)
         if o_type == "r_byol":
             raise NotImplementedError("o_type='r_byol' reads an attribute the reference never sets (self.shuffle_bn, "
                                       "i3d_byol.py:777); use o_type='loss_com'")

@@ -112,7 +112,7 @@ class PackPlan:
         if self.state == "record":
             lib.cstp_pack_mode(1)
             try:
-                fn()
+                out = fn()
             finally:
                 lib.cstp_pack_mode(0)
                 n = lib.cstp_pack_recorded(None, 0)
@@ -123,9 +123,10 @@ class PackPlan:
         else:
             # (replay state: the call's workspace is REGISTERED with the library -- cstp_pack_register -- so the call skips its pack
             #  without any per-call switch; the host spends one dictionary lookup here)
-            fn()
+            out = fn()
             if self.state == "replay" and key in self.recs:
                 self.stats["skipped_calls"] += 1
+        return out
 
     def finish_record(self, device):
         """Build the per-group device tables from what the recording step collected."""
@@ -206,20 +207,13 @@ def _dispatch_facts(operands, absmax):
 def _packed_call(w_param, tag, x_shape, device, nbytes, fn, facts=()):
     """``fn(ws)`` = one C-ABI convolution call that packs ``w_param`` into its workspace: through the pack plan when a
     training step has armed one (persistent workspace, recorded / skipped pack), else on the shared scratch arena.
-    ``facts``: _dispatch_facts of the call (part of the plan's key)."""
+    ``facts``: _dispatch_facts of the call (part of the plan's key).  Returns what ``fn`` returns."""
     plan = pack_plan
     if plan is None or not plan.armed or plan.state == "off" or w_param is None:
-        ws = _workspace(device, nbytes)
-        fn(ws)
-        return
+        return fn(_workspace(device, nbytes))
     key = PackPlan.key(w_param, tag, x_shape, facts)
     ws = plan.workspace(key, device, nbytes)
-    if plan.state == "record":
-        plan.call(key, lambda: fn(ws))
-    else:
-        fn(ws)
-        if plan.state == "replay" and key in plan.recs:
-            plan.stats["skipped_calls"] += 1
+    return plan.call(key, lambda: fn(ws))
 
 
 def _req(t: torch.Tensor, name: str) -> torch.Tensor:
@@ -336,6 +330,7 @@ def _table_key(arith, mode, desc):
 
 
 def _autotune(lib, desc, mode, src, w, out, ws):
+    """``out``: the tensor the timed candidates may overwrite, or a factory of one (called only if the geometry is timed)."""
     global _table_dirty
     arith = lib.cstp_gemm_get_split_terms()
     key = (arith, mode) + tuple(getattr(desc, f) for f, _ in ConvDesc._fields_)
@@ -352,6 +347,8 @@ def _autotune(lib, desc, mode, src, w, out, ws):
         if lib.cstp_conv3d_set_tile(ctypes.byref(desc), mode, arr) == 0:
             tune_stats["from_table"] += 1
             return
+    if callable(out):
+        out = out()
     check(lib.cstp_conv3d_autotune(_stream(), ctypes.byref(desc), mode, src.data_ptr(), w.data_ptr(), out.data_ptr(),
                                    ws.data_ptr(), ws.numel(), 2), "cstp_conv3d_autotune")
     tune_stats["timed"] += 1
@@ -490,6 +487,34 @@ def _queue_join(device: torch.device) -> None:
         _join_pending.add(device.index)
 
 
+def _place_wgrad(param, w, need, side_ok, wgrad, reads):
+    """Where a convolution's weight gradient goes; returns what autograd is handed for the weight.  ``wgrad(dst, accumulate)``
+    launches the kernel.  The gradient of a leaf weight whose .grad is a contiguous slice of the flat gradient arena
+    (mark_direct_grad) is ADDED there by the library itself -- AccumulateGrad folded into the unpacking pass: no temporary, no
+    add kernel -- and autograd sees None.  With ``side_ok`` and OVERLAP_WGRAD it also runs on a second HIP stream: it feeds nothing
+    downstream in the backward chain, so the matrix-core-bound weight-gradient kernels execute beside the HBM-bound BatchNorm
+    backward kernels of the main chain (the arena is joined before anything reads it, _join_side_streams).  ``reads``: the
+    tensors the kernel reads (None entries skipped), kept alive for the side stream."""
+    if not need:
+        return None
+    if not _direct(param):
+        dw = torch.empty_like(w)
+        wgrad(dw, False)
+        return dw
+    if side_ok and OVERLAP_WGRAD:
+        side = _side_stream(w.device)
+        side.wait_stream(torch.cuda.current_stream(w.device))      # dy is complete
+        with torch.cuda.stream(side):
+            wgrad(param.grad, True)
+        for t in reads:
+            if t is not None:
+                t.record_stream(side)
+        _queue_join(w.device)
+    else:
+        wgrad(param.grad, True)
+    return None
+
+
 # ----------------------------------------------------------------------------------------------
 # convolution / linear
 # ----------------------------------------------------------------------------------------------
@@ -568,6 +593,64 @@ class GradJoin:
                                "input gradient was pruned; the block input's gradient would have been dropped" % (len(left), left))
 
 
+def _tune(desc, mode, src, w, out, ws):
+    """Give this geometry and direction its tile on first sight (_autotune).  ``out`` may be a factory: tuning overwrites its
+    output, and a scratch tensor is only worth allocating when candidates are really timed."""
+    if AUTOTUNE:
+        _autotune(_lib.load(), desc, mode, src, w, out, ws)
+
+
+def _launch_forward(desc, x, w, bias, aff, y, ws, cell, groups, pivot):
+    """The forward convolution launch (fp32).  ``aff``: an InAffine applied inside the gather, else None; ``cell``: the absmax cell
+    of the (transformed) input.  ``groups`` > 0: a train-mode BatchNorm over that many slices of the batch consumes y; where the
+    layer's kernel can, it leaves the statistics' partial sums beside y (cstp_conv3d_forward_bnstats) and the BatchNorm skips
+    its pass over the tensor; ``pivot``: the value the sums are taken around.  Returns (partials, nsplit, groups, cell of y) when
+    the kernel left them, else None."""
+    lib = _lib.load()
+    nsplit = lib.cstp_conv3d_bnstats_nsplit if aff is None else lib.cstp_conv3d_bnstats_nsplit_aff
+    ns = nsplit(ctypes.byref(desc), groups) if (groups > 0 and bias is None and FUSE_BN_STATS) else 0
+    a = None if aff is None else ctypes.byref(aff)
+    if ns <= 0:
+        check(lib.cstp_conv3d_forward_am(_stream(), ctypes.byref(desc), x.data_ptr(), w.data_ptr(), _ptr(bias), a, y.data_ptr(),
+                                         ws.data_ptr(), ws.numel(), _ptr(cell)), "cstp_conv3d_forward")
+        return None
+    k = w.shape[0]
+    # sums [k][groups][ns][2], pivots [k], then the (min, max) keys [k][groups][ns][2] as uint32 (one double each)
+    part = torch.empty(k * groups * ns * 3 + k, dtype=torch.float64, device=x.device)
+    ycell = torch.empty(1, dtype=torch.int32, device=x.device)
+    got = ctypes.c_int32(0)
+    pv = None if pivot is None else _req(pivot, "BatchNorm pivot")
+    if pv is not None and pv.numel() != k:
+        raise _lib.CstpError("BatchNorm pivot has %d entries for %d output channels" % (pv.numel(), k))
+    check(lib.cstp_conv3d_forward_bnstats(_stream(), ctypes.byref(desc), x.data_ptr(), w.data_ptr(), y.data_ptr(), ws.data_ptr(),
+                                          ws.numel(), _ptr(cell), groups, _ptr(pv), part.data_ptr(), part.numel() * 8,
+                                          ctypes.byref(got), ycell.data_ptr(), a), "cstp_conv3d_forward_bnstats")
+    return (part, got.value, groups, ycell) if got.value > 0 else None
+
+
+def _own_pack(w, param):
+    """The parameter whose pack a call may leave to the pack plan: ``param`` itself, unless _req had to copy it."""
+    return param if w.data_ptr() == param.data_ptr() else None
+
+
+def _data_grad(desc, x, w, param, dy, cell, nbytes, launch, join=None):
+    """The data gradient of a convolution.  ``launch(dst, ws, accumulate)`` is the C-ABI call, ``cell`` the absmax cell of dy.
+    ``join``: x also feeds another op (GradJoin): the sum of the two gradients is formed in this kernel's epilogue."""
+    b16 = x.dtype == torch.bfloat16
+
+    def dgrad(dst, acc):
+        if not b16:       # (tuning overwrites its output)
+            _tune(desc, 1, dy, w, lambda: torch.empty_like(dst) if acc else dst, _workspace(x.device, nbytes))
+        with _span("conv3d_backward_data", lambda: (("bf16",) if b16 else ()) + _desc_key(desc)):
+            _packed_call(_own_pack(w, param), "d", x.shape, x.device, nbytes, lambda ws: launch(dst, ws, acc),
+                         _dispatch_facts((dy, dst), cell))
+        return dst
+
+    if join is None:
+        return dgrad(torch.empty_like(x), False)
+    return join.contribute(lambda: dgrad(torch.empty_like(x), False), lambda buf: dgrad(buf, True))
+
+
 class _Conv3d(torch.autograd.Function):
     _last_stats = None
 
@@ -583,35 +666,11 @@ class _Conv3d(torch.autograd.Function):
         nbytes = lib.cstp_conv3d_workspace_bytes(ctypes.byref(desc))
         ws = _workspace(x.device, nbytes)
         b = None if bias is None else _req(bias, "conv3d bias")
-        if AUTOTUNE:
-            _autotune(lib, desc, 0, x, w, y, ws)
-        # a train-mode BatchNorm over bn_groups slices of the batch consumes y: where the layer's kernel can, it leaves the
-        # statistics' partial sums beside y (cstp_conv3d_forward_bnstats) and batch_norm_act skips its pass over the tensor
-        ns = lib.cstp_conv3d_bnstats_nsplit(ctypes.byref(desc), bn_groups) if (bn_groups > 0 and b is None and FUSE_BN_STATS) else 0
-        _Conv3d._last_stats = None
-
-        def run(ws):
-            if ns > 0:
-                # sums [k][groups][ns][2], pivots [k], then the (min, max) keys [k][groups][ns][2] as uint32 (one double each)
-                part = torch.empty(w.shape[0] * bn_groups * ns * 3 + w.shape[0], dtype=torch.float64, device=x.device)
-                zcell = torch.empty(1, dtype=torch.int32, device=x.device)
-                got = ctypes.c_int32(0)
-                pv = None if bn_pivot is None else _req(bn_pivot, "BatchNorm pivot")
-                if pv is not None and pv.numel() != w.shape[0]:
-                    raise _lib.CstpError("BatchNorm pivot has %d entries for %d output channels" % (pv.numel(), w.shape[0]))
-                check(lib.cstp_conv3d_forward_bnstats(_stream(), ctypes.byref(desc), x.data_ptr(), w.data_ptr(), y.data_ptr(),
-                                                      ws.data_ptr(), ws.numel(), _ptr(xam), bn_groups, _ptr(pv), part.data_ptr(),
-                                                      part.numel() * 8, ctypes.byref(got), zcell.data_ptr(), None),
-                      "cstp_conv3d_forward_bnstats")
-                if got.value > 0:
-                    _Conv3d._last_stats = (part, got.value, bn_groups, zcell)
-            else:
-                check(lib.cstp_conv3d_forward_am(_stream(), ctypes.byref(desc), x.data_ptr(), w.data_ptr(), _ptr(b), None,
-                                                 y.data_ptr(), ws.data_ptr(), ws.numel(), _ptr(xam)), "cstp_conv3d_forward")
-
+        _tune(desc, 0, x, w, y, ws)
         with _span("conv3d_forward", lambda: _desc_key(desc)):
-            _packed_call(w_in if w.data_ptr() == w_in.data_ptr() else None, "f", x.shape, x.device, nbytes, run,
-                         _dispatch_facts((x, y), xam))
+            _Conv3d._last_stats = _packed_call(
+                _own_pack(w, w_in), "f", x.shape, x.device, nbytes,
+                lambda ws: _launch_forward(desc, x, w, b, None, y, ws, xam, bn_groups, bn_pivot), _dispatch_facts((x, y), xam))
         ctx.save_for_backward(x, w)
         ctx.w_param = w_in           # the parameter object itself (save_for_backward hands back a new tensor object)
         ctx.grad_join = grad_join
@@ -630,62 +689,30 @@ class _Conv3d(torch.autograd.Function):
         dy = _req(dy, "conv3d grad_output")
         nbytes = lib.cstp_conv3d_workspace_bytes(ctypes.byref(desc))
         dx = dw = db = None
-        # The gradient of a leaf weight whose .grad is a contiguous slice of the flat gradient arena (DIRECT_WGRAD) is ADDED
-        # there by the library itself -- AccumulateGrad folded into the unpacking pass: no temporary, no add kernel -- and
-        # autograd sees None for this input.  With OVERLAP_WGRAD it also runs on a second HIP stream: it feeds nothing
-        # downstream in the backward chain, so the matrix-core-bound weight-gradient kernels execute beside the HBM-bound
-        # BatchNorm backward kernels of the main chain (the arena is joined before anything reads it, _join_side_streams).
-        direct_w = ctx.needs_input_grad[1] and _direct(ctx.w_param)
-        side_w = direct_w and OVERLAP_WGRAD and x.dim() == 5 and x.shape[2] * x.shape[3] * x.shape[4] > 1
+        need_w, pw = ctx.needs_input_grad[1], ctx.w_param
+        # (a 5-D input with more than one position: a linear layer's weight gradient never goes to the side stream)
+        side_w = need_w and _direct(pw) and OVERLAP_WGRAD and x.dim() == 5 and x.shape[2] * x.shape[3] * x.shape[4] > 1
 
-        def wgrad_into_arena():
+        def wgrad(dst, accumulate):
             wsx = _workspace(x.device, nbytes)
-            if AUTOTUNE and (lib.cstp_gemm_get_split_terms(), 2) + _desc_key(desc) not in _tuned:
-                _autotune(lib, desc, 2, x, dy, torch.empty_like(w), wsx)          # (tuning overwrites its output)
+            _tune(desc, 2, x, dy, lambda: torch.empty_like(dst) if accumulate else dst, wsx)     # (tuning overwrites its output)
             with _span("conv3d_backward_weight", lambda: _desc_key(desc)):
                 check(lib.cstp_conv3d_backward_weight_acc(_stream(), ctypes.byref(desc), x.data_ptr(), None, dy.data_ptr(),
-                                                          ctx.w_param.grad.data_ptr(), wsx.data_ptr(), wsx.numel(), _ptr(xam),
-                                                          _ptr(dyam), 1), "cstp_conv3d_backward_weight")
+                                                          dst.data_ptr(), wsx.data_ptr(), wsx.numel(), _ptr(xam), _ptr(dyam),
+                                                          1 if accumulate else 0), "cstp_conv3d_backward_weight")
 
-        if side_w:
-            main = torch.cuda.current_stream(x.device)
-            side = _side_stream(x.device)
-            side.wait_stream(main)                     # dy is complete
-            with torch.cuda.stream(side):
-                wgrad_into_arena()
-            x.record_stream(side)
-            dy.record_stream(side)
-            for cell in (xam, dyam):                   # the cells are read by the side-stream kernels too
-                if cell is not None:
-                    cell.record_stream(side)
-            _queue_join(x.device)
+        def place():
+            return _place_wgrad(pw, w, need_w, side_w, wgrad, (x, dy, xam, dyam))
+
+        if side_w:       # ahead of the data gradient, beside it
+            dw = place()
         if ctx.needs_input_grad[0]:
-            def dgrad(dst, acc):
-                if AUTOTUNE and (lib.cstp_gemm_get_split_terms(), 1) + _desc_key(desc) not in _tuned:
-                    _autotune(lib, desc, 1, dy, w, torch.empty_like(dst) if acc else dst, _workspace(x.device, nbytes))   # (tuning overwrites its output)
-                with _span("conv3d_backward_data", lambda: _desc_key(desc)):
-                    _packed_call(ctx.w_param if w.data_ptr() == ctx.w_param.data_ptr() else None, "d", x.shape, x.device, nbytes,
-                                 lambda ws: check(lib.cstp_conv3d_backward_data_acc(
-                                     _stream(), ctypes.byref(desc), dy.data_ptr(), w.data_ptr(), dst.data_ptr(), ws.data_ptr(),
-                                     ws.numel(), _ptr(dyam), 1 if acc else 0), "cstp_conv3d_backward_data"),
-                                 _dispatch_facts((dy, dst), dyam))
-                return dst
-            join = ctx.grad_join
-            if join is None:
-                dx = dgrad(torch.empty_like(x), False)
-            else:       # x also feeds another op: the sum of the two gradients is formed here (GradJoin)
-                dx = join.contribute(lambda: dgrad(torch.empty_like(x), False), lambda buf: dgrad(buf, True))
-        if direct_w and not side_w:
-            wgrad_into_arena()
-        elif ctx.needs_input_grad[1] and not direct_w:
-            dw = torch.empty_like(w)
-            ws = _workspace(x.device, nbytes)
-            if AUTOTUNE:
-                _autotune(lib, desc, 2, x, dy, dw, ws)
-            with _span("conv3d_backward_weight", lambda: _desc_key(desc)):
-                check(lib.cstp_conv3d_backward_weight_am(_stream(), ctypes.byref(desc), x.data_ptr(), None, dy.data_ptr(),
-                                                         dw.data_ptr(), ws.data_ptr(), ws.numel(), _ptr(xam), _ptr(dyam)),
-                      "cstp_conv3d_backward_weight")
+            dx = _data_grad(desc, x, w, pw, dy, dyam, nbytes,
+                            lambda dst, ws, acc: check(lib.cstp_conv3d_backward_data_acc(
+                                _stream(), ctypes.byref(desc), dy.data_ptr(), w.data_ptr(), dst.data_ptr(), ws.data_ptr(), ws.numel(),
+                                _ptr(dyam), 1 if acc else 0), "cstp_conv3d_backward_data"), ctx.grad_join)
+        if not side_w:   # on the main stream: behind the data gradient, which the backward chain waits for
+            dw = place()
         if ctx.has_bias and ctx.needs_input_grad[2]:
             n, k = dy.shape[0], dy.shape[1]
             s = dy.numel() // (n * k)
@@ -730,6 +757,27 @@ def linear(x, w, bias=None):
 # ----------------------------------------------------------------------------------------------
 # train-mode BatchNorm (+ residual) (+ ReLU)
 # ----------------------------------------------------------------------------------------------
+def _bn_operands(req, x, residual, groups=1):
+    """(x, residual, n, c, s) of a BatchNorm call, checked; ``req``: _req (fp32 activations) or _req16 (bf16 storage)."""
+    x = req(x, "batch_norm input")
+    n, c = x.shape[0], x.shape[1]
+    res = None if residual is None else req(residual, "residual")
+    if res is not None and res.shape != x.shape:
+        raise _lib.CstpError("residual shape %s != input shape %s" % (tuple(res.shape), tuple(x.shape)))
+    if groups < 1 or n % groups != 0:
+        raise _lib.CstpError("batch of %d rows cannot be split into %d BN groups" % (n, groups))
+    return x, res, n, c, x.numel() // (n * c)
+
+
+def _bn_param_grads(need_gamma, need_beta, pg, pb, gamma):
+    """(direct, dgamma, dbeta) of a BatchNorm backward.  Parameters whose .grad is a live slice of the flat gradient arena
+    (cstp_amd.train): the kernel adds into it directly (``direct``) and autograd is handed None for both."""
+    direct = need_gamma and need_beta and _direct(pg) and _direct(pb)
+    if direct:
+        return True, pg.grad, pb.grad
+    return False, torch.empty_like(gamma), torch.empty_like(gamma)
+
+
 class _BNAct(torch.autograd.Function):
     _last_cell = None
     _pre_stats = None     # (partial sums, nsplit) the producing convolution left for this call (batch_norm_act sets it)
@@ -737,16 +785,9 @@ class _BNAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, residual, running_mean, running_var, relu, eps, momentum, groups, grad_join=None):
         lib = _lib.load()
-        x = _req(x, "batch_norm input")
+        x, res, n, c, s = _bn_operands(_req, x, residual, groups)
         gamma = _req(gamma, "batch_norm weight")
         beta = _req(beta, "batch_norm bias")
-        n, c = x.shape[0], x.shape[1]
-        s = x.numel() // (n * c)
-        res = None if residual is None else _req(residual, "residual")
-        if res is not None and res.shape != x.shape:
-            raise _lib.CstpError("residual shape %s != input shape %s" % (tuple(res.shape), tuple(x.shape)))
-        if groups < 1 or n % groups != 0:
-            raise _lib.CstpError("batch of %d rows cannot be split into %d BN groups" % (n, groups))
         y = torch.empty_like(x)
         mean = torch.empty(groups * c, dtype=torch.float32, device=x.device)
         invstd = torch.empty(groups * c, dtype=torch.float32, device=x.device)
@@ -793,11 +834,7 @@ class _BNAct(torch.autograd.Function):
         s = x.numel() // (n * c)
         dx = torch.empty_like(x)
         dres = torch.empty_like(x) if (ctx.has_res and ctx.needs_input_grad[3]) else None
-        # parameters whose .grad is a live slice of the flat gradient arena (cstp_amd.train): the kernel adds into it directly
-        pg, pb = ctx.params
-        direct = ctx.needs_input_grad[1] and ctx.needs_input_grad[2] and _direct(pg) and _direct(pb)
-        dgamma = pg.grad if direct else torch.empty_like(gamma)
-        dbeta = pb.grad if direct else torch.empty_like(gamma)
+        direct, dgamma, dbeta = _bn_param_grads(ctx.needs_input_grad[1], ctx.needs_input_grad[2], *ctx.params, gamma)
         nbytes = lib.cstp_bn_workspace_bytes(n, c, s, ctx.groups)
         ws = _workspace(x.device, nbytes)
         cell = _new_cell(x) if s > 1 else None
@@ -810,7 +847,7 @@ class _BNAct(torch.autograd.Function):
         if dres is not None and ctx.grad_join is not None:       # the residual tensor's other consumer adds its gradient to this
             dres = ctx.grad_join.contribute(lambda: dres, lambda buf: buf.add_(dres))
         if direct:
-            return dx, None, None, dres, None, None, None, None, None, None, None
+            dgamma = dbeta = None
         return dx, dgamma, dbeta, dres, None, None, None, None, None, None, None
 
 
@@ -839,23 +876,14 @@ def batch_norm_eval(x, gamma, beta, running_mean, running_var, residual=None, re
         raise _lib.CstpError("eval-mode BatchNorm is forward-only: call it under torch.no_grad() (as the reference's "
                              "validation/test loops do)")
     if x.dtype == torch.bfloat16:          # the bf16-storage path
-        x = _req16(x, "batch_norm input")
-        n, c = x.shape[0], x.shape[1]
-        res = None if residual is None else _req16(residual, "residual")
-        if res is not None and res.shape != x.shape:
-            raise _lib.CstpError("residual shape %s != input shape %s" % (tuple(res.shape), tuple(x.shape)))
+        x, res, n, c, s = _bn_operands(_req16, x, residual)
         y = torch.empty_like(x)
         check(lib.cstp_b16_bn_forward_eval(_stream(), x.data_ptr(), _ptr(res), y.data_ptr(), _req(gamma, "weight").data_ptr(),
                                            _req(beta, "bias").data_ptr(), _req(running_mean, "running_mean").data_ptr(),
-                                           _req(running_var, "running_var").data_ptr(), n, c, x.numel() // (n * c), float(eps),
+                                           _req(running_var, "running_var").data_ptr(), n, c, s, float(eps),
                                            1 if relu else 0), "cstp_b16_bn_forward_eval")
         return y
-    x = _req(x, "batch_norm input")
-    n, c = x.shape[0], x.shape[1]
-    s = x.numel() // (n * c)
-    res = None if residual is None else _req(residual, "residual")
-    if res is not None and res.shape != x.shape:
-        raise _lib.CstpError("residual shape %s != input shape %s" % (tuple(res.shape), tuple(x.shape)))
+    x, res, n, c, s = _bn_operands(_req, x, residual)
     y = torch.empty_like(x)
     cell = _new_cell(x) if s > 1 else None
     ws = _workspace(x.device, lib.cstp_bn_workspace_bytes(n, c, s, 1) if cell is not None else lib.cstp_bn_eval_workspace_bytes(c))
@@ -909,35 +937,16 @@ class _BNReluConv3d(torch.autograd.Function):
                                               eps, momentum, ws.data_ptr(), ws.numel()), "cstp_bn_stats_train")
         desc = _desc(x.shape, w.shape, stride, padding)
         y = torch.empty(conv_out_shape(x.shape, w.shape, stride, padding), dtype=torch.float32, device=x.device)
-        ws = _workspace(x.device, lib.cstp_conv3d_workspace_bytes(ctypes.byref(desc)))
-        if AUTOTUNE:
-            _autotune(lib, desc, 0, x, w, y, ws)
+        nbytes = lib.cstp_conv3d_workspace_bytes(ctypes.byref(desc))
+        _tune(desc, 0, x, w, y, _workspace(x.device, nbytes))
         aff = InAffine(ss.data_ptr(), groups, 1 if relu else 0)
         # a train-mode BatchNorm over out_groups slices consumes y: where this layer's kernel can, it leaves that BatchNorm's
         # sums and range beside y (the temporal patch kernel igemm_k1t<.., STATS, AFF>)
-        ns = lib.cstp_conv3d_bnstats_nsplit_aff(ctypes.byref(desc), out_groups) if (out_groups > 0 and FUSE_BN_STATS) else 0
-        _BNReluConv3d._last_stats = None
-
-        def run(ws):
-            if ns > 0:
-                part = torch.empty(w.shape[0] * out_groups * ns * 3 + w.shape[0], dtype=torch.float64, device=x.device)
-                ycell = torch.empty(1, dtype=torch.int32, device=x.device)
-                got = ctypes.c_int32(0)
-                pv = None if out_pivot is None else _req(out_pivot, "BatchNorm pivot")
-                check(lib.cstp_conv3d_forward_bnstats(_stream(), ctypes.byref(desc), x.data_ptr(), w.data_ptr(), y.data_ptr(),
-                                                      ws.data_ptr(), ws.numel(), _ptr(zam), out_groups, _ptr(pv), part.data_ptr(),
-                                                      part.numel() * 8, ctypes.byref(got), ycell.data_ptr(), ctypes.byref(aff)),
-                      "cstp_conv3d_forward_bnstats")
-                if got.value > 0:
-                    _BNReluConv3d._last_stats = (part, got.value, out_groups, ycell)
-            else:
-                check(lib.cstp_conv3d_forward_am(_stream(), ctypes.byref(desc), x.data_ptr(), w.data_ptr(), None, ctypes.byref(aff),
-                                                 y.data_ptr(), ws.data_ptr(), ws.numel(), _ptr(zam)), "cstp_conv3d_forward")
-
         with _span("conv3d_forward", lambda: _desc_key(desc)):
             # ("fa": a forward that carries the in_affine may run another kernel variant -- another pack -- than the plain one)
-            _packed_call(w_in if w.data_ptr() == w_in.data_ptr() else None, "fa", x.shape, x.device,
-                         lib.cstp_conv3d_workspace_bytes(ctypes.byref(desc)), run, _dispatch_facts((x, y), zam))
+            _BNReluConv3d._last_stats = _packed_call(
+                _own_pack(w, w_in), "fa", x.shape, x.device, nbytes,
+                lambda ws: _launch_forward(desc, x, w, None, aff, y, ws, zam, out_groups, out_pivot), _dispatch_facts((x, y), zam))
         ctx.save_for_backward(x, gamma, mean, invstd, ss, w)
         ctx.desc, ctx.groups, ctx.relu, ctx.z_absmax = desc, groups, relu, zam
         ctx.params = (g_in, b_in, w_in)      # the parameter objects themselves (their .grad may be an arena slice)
@@ -953,53 +962,29 @@ class _BNReluConv3d(torch.autograd.Function):
         dy = _req(dy, "bn_relu_conv3d grad_output")
         n, c = x.shape[0], x.shape[1]
         s = x.numel() // (n * c)
-        nbytes = max(lib.cstp_conv3d_workspace_bytes(ctypes.byref(desc)), lib.cstp_bn_workspace_bytes(n, c, s, ctx.groups))
+        cbytes = lib.cstp_conv3d_workspace_bytes(ctypes.byref(desc))
+        nbytes = max(cbytes, lib.cstp_bn_workspace_bytes(n, c, s, ctx.groups))
         aff = InAffine(ss.data_ptr(), ctx.groups, 1 if ctx.relu else 0)
-        dw = None
-        direct_w = ctx.needs_input_grad[5] and _direct(pw)
-        side_w = direct_w and OVERLAP_WGRAD
 
         def wgrad(dst, accumulate):
             wsx = _workspace(x.device, nbytes)
-            if AUTOTUNE and (lib.cstp_gemm_get_split_terms(), 2) + _desc_key(desc) not in _tuned:
-                _autotune(lib, desc, 2, x, dy, torch.empty_like(w), wsx)          # (tuning overwrites its output)
+            _tune(desc, 2, x, dy, lambda: torch.empty_like(w), wsx)          # (tuning overwrites its output)
             with _span("conv3d_backward_weight", lambda: _desc_key(desc)):
                 check(lib.cstp_conv3d_backward_weight_acc(_stream(), ctypes.byref(desc), x.data_ptr(), ctypes.byref(aff),
                                                           dy.data_ptr(), dst.data_ptr(), wsx.data_ptr(), wsx.numel(), _ptr(zam),
                                                           _ptr(dyam), 1 if accumulate else 0), "cstp_conv3d_backward_weight")
 
-        if side_w:       # as _Conv3d.backward: the weight gradient feeds nothing downstream in the backward chain
-            main = torch.cuda.current_stream(x.device)
-            side = _side_stream(x.device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                wgrad(pw.grad, True)
-            for t in (x, dy, ss, zam, dyam):
-                if t is not None:
-                    t.record_stream(side)
-            _queue_join(x.device)
-        elif direct_w:
-            wgrad(pw.grad, True)
-        elif ctx.needs_input_grad[5]:
-            dw = torch.empty_like(w)
-            wgrad(dw, False)
+        dw = _place_wgrad(pw, w, ctx.needs_input_grad[5], True, wgrad, (x, dy, ss, zam, dyam))
         dx = dgamma = dbeta = None
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             ws = _workspace(x.device, nbytes)
-            dz = torch.empty_like(x)     # gradient w.r.t. the (never materialised) normalised activation
-            if AUTOTUNE and (lib.cstp_gemm_get_split_terms(), 1) + _desc_key(desc) not in _tuned:
-                _autotune(lib, desc, 1, dy, w, dz, ws)
-            with _span("conv3d_backward_data", lambda: _desc_key(desc)):
-                _packed_call(pw if w.data_ptr() == pw.data_ptr() else None, "d", x.shape, x.device,
-                             lib.cstp_conv3d_workspace_bytes(ctypes.byref(desc)),
-                             lambda wsd: check(lib.cstp_conv3d_backward_data_acc(
-                                 _stream(), ctypes.byref(desc), dy.data_ptr(), w.data_ptr(), dz.data_ptr(), wsd.data_ptr(),
-                                 wsd.numel(), _ptr(dyam), 0), "cstp_conv3d_backward_data"),
-                             _dispatch_facts((dy, dz), dyam))
+            # dz: the gradient w.r.t. the (never materialised) normalised activation
+            dz = _data_grad(desc, x, w, pw, dy, dyam, cbytes,
+                            lambda dst, wsd, acc: check(lib.cstp_conv3d_backward_data_acc(
+                                _stream(), ctypes.byref(desc), dy.data_ptr(), w.data_ptr(), dst.data_ptr(), wsd.data_ptr(),
+                                wsd.numel(), _ptr(dyam), 1 if acc else 0), "cstp_conv3d_backward_data"))
             dx = torch.empty_like(x)
-            direct = ctx.needs_input_grad[1] and ctx.needs_input_grad[2] and _direct(pg) and _direct(pb)
-            dgamma = pg.grad if direct else torch.empty_like(gamma)
-            dbeta = pb.grad if direct else torch.empty_like(gamma)
+            direct, dgamma, dbeta = _bn_param_grads(ctx.needs_input_grad[1], ctx.needs_input_grad[2], pg, pb, gamma)
             cell = _new_cell(x)
             with _span("bn_backward", (n, c, s, ctx.groups, False, bool(ctx.relu))):
                 check(lib.cstp_bn_backward_am(_stream(), x.data_ptr(), None, dz.data_ptr(), gamma.data_ptr(), mean.data_ptr(),
@@ -1476,7 +1461,7 @@ class _Conv3dB16(torch.autograd.Function):
         y = torch.empty(conv_out_shape(x.shape, w.shape, stride, padding), dtype=torch.bfloat16, device=x.device)
         nbytes = lib.cstp_b16_conv3d_workspace_bytes(ctypes.byref(desc))
         with _span("conv3d_forward", lambda: ("bf16",) + _desc_key(desc)):
-            _packed_call(w_in if w.data_ptr() == w_in.data_ptr() else None, "f", x.shape, x.device, nbytes,
+            _packed_call(_own_pack(w, w_in), "f", x.shape, x.device, nbytes,
                          lambda ws: check(lib.cstp_b16_conv3d_forward(_stream(), ctypes.byref(desc), x.data_ptr(), w.data_ptr(), y.data_ptr(),
                                                                       ws.data_ptr(), ws.numel()), "cstp_b16_conv3d_forward"),
                          _dispatch_facts((x, y), None))
@@ -1492,8 +1477,7 @@ class _Conv3dB16(torch.autograd.Function):
         desc = ctx.desc
         dy = _req16(dy, "conv3d grad_output")
         nbytes = lib.cstp_b16_conv3d_workspace_bytes(ctypes.byref(desc))
-        dx = dw = None
-        direct_w = ctx.needs_input_grad[1] and _direct(ctx.w_param)
+        dx = None
 
         def wgrad(dst, accumulate):
             wsx = _workspace(x.device, nbytes)
@@ -1502,34 +1486,12 @@ class _Conv3dB16(torch.autograd.Function):
                                                           wsx.data_ptr(), wsx.numel(), 1 if accumulate else 0),
                       "cstp_b16_conv3d_backward_weight")
 
-        if direct_w and OVERLAP_WGRAD:      # as _Conv3d.backward: the weight gradient feeds nothing downstream in the chain
-            main = torch.cuda.current_stream(x.device)
-            side = _side_stream(x.device)
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                wgrad(ctx.w_param.grad, True)
-            x.record_stream(side)
-            dy.record_stream(side)
-            _queue_join(x.device)
-        elif direct_w:
-            wgrad(ctx.w_param.grad, True)
-        elif ctx.needs_input_grad[1]:
-            dw = torch.empty_like(w)
-            wgrad(dw, False)
+        dw = _place_wgrad(ctx.w_param, w, ctx.needs_input_grad[1], True, wgrad, (x, dy))
         if ctx.needs_input_grad[0]:
-            def dgrad(dst, acc):
-                with _span("conv3d_backward_data", lambda: ("bf16",) + _desc_key(desc)):
-                    _packed_call(ctx.w_param if w.data_ptr() == ctx.w_param.data_ptr() else None, "d", x.shape, x.device, nbytes,
-                                 lambda ws: check(lib.cstp_b16_conv3d_backward_data_acc(
-                                     _stream(), ctypes.byref(desc), dy.data_ptr(), w.data_ptr(), dst.data_ptr(), ws.data_ptr(), ws.numel(),
-                                     1 if acc else 0), "cstp_b16_conv3d_backward_data"),
-                                 _dispatch_facts((dy, dst), None))
-                return dst
-            join = ctx.grad_join
-            if join is None:
-                dx = dgrad(torch.empty_like(x), False)
-            else:       # x also feeds another op (the residual connection): the sum of the two gradients is formed here (GradJoin)
-                dx = join.contribute(lambda: dgrad(torch.empty_like(x), False), lambda buf: dgrad(buf, True))
+            dx = _data_grad(desc, x, w, ctx.w_param, dy, None, nbytes,
+                            lambda dst, ws, acc: check(lib.cstp_b16_conv3d_backward_data_acc(
+                                _stream(), ctypes.byref(desc), dy.data_ptr(), w.data_ptr(), dst.data_ptr(), ws.data_ptr(), ws.numel(),
+                                1 if acc else 0), "cstp_b16_conv3d_backward_data"), ctx.grad_join)
         return dx, dw, None, None, None
 
 
@@ -1539,16 +1501,9 @@ class _BNActB16(torch.autograd.Function):
         lib = _lib.load()
         ctx.param_objs = (gamma, beta)     # the parameter objects themselves (their .grad may be an arena slice)
         ctx.grad_join = grad_join
-        x = _req16(x, "batch_norm input")
+        x, res, n, c, s = _bn_operands(_req16, x, residual, groups)
         gamma = _req(gamma, "batch_norm weight")
         beta = _req(beta, "batch_norm bias")
-        n, c = x.shape[0], x.shape[1]
-        s = x.numel() // (n * c)
-        res = None if residual is None else _req16(residual, "residual")
-        if res is not None and res.shape != x.shape:
-            raise _lib.CstpError("residual shape %s != input shape %s" % (tuple(res.shape), tuple(x.shape)))
-        if groups < 1 or n % groups != 0:
-            raise _lib.CstpError("batch of %d rows cannot be split into %d BN groups" % (n, groups))
         y = torch.empty_like(x)
         mean = torch.empty(groups * c, dtype=torch.float32, device=x.device)
         invstd = torch.empty(groups * c, dtype=torch.float32, device=x.device)
@@ -1575,10 +1530,7 @@ class _BNActB16(torch.autograd.Function):
         s = x.numel() // (n * c)
         dx = torch.empty_like(x)
         dres = torch.empty_like(x) if (ctx.has_res and ctx.needs_input_grad[3]) else None
-        pg, pb = ctx.param_objs
-        direct = ctx.needs_input_grad[1] and ctx.needs_input_grad[2] and _direct(pg) and _direct(pb)
-        dgamma = pg.grad if direct else torch.empty_like(gamma)
-        dbeta = pb.grad if direct else torch.empty_like(gamma)
+        direct, dgamma, dbeta = _bn_param_grads(ctx.needs_input_grad[1], ctx.needs_input_grad[2], *ctx.param_objs, gamma)
         ws = _workspace(x.device, lib.cstp_b16_bn_workspace_bytes(n, c, s, ctx.groups))
         with _span("bn_backward", (n, c, s, ctx.groups, ctx.has_res, bool(ctx.relu), "bf16")):
             check(lib.cstp_b16_bn_backward(_stream(), x.data_ptr(), _ptr(y), dy.data_ptr(), gamma.data_ptr(), mean.data_ptr(),

@@ -48,7 +48,7 @@ def _temporal_fused(x, conv, groups) -> bool:
 
 
 # Run the (no-grad) target-network forward on a second HIP stream, staggered behind the online network's stem + conv2 stage
-# (R21DBYOL.forward): -2.5 ms/step at cfg2 on MI355X.  CSTP_OVERLAP_TARGET=0 runs the two forwards back to back.
+# (ByolBase._two_view_step, every backbone): -2.5 ms/step at cfg2 on MI355X.  CSTP_OVERLAP_TARGET=0 runs the two forwards back to back.
 OVERLAP_TARGET_FORWARD = os.environ.get("CSTP_OVERLAP_TARGET", "1") == "1"
 
 
@@ -134,7 +134,7 @@ class _BatchNorm(nn.Module):
         y = ops.batch_norm_act(x, self.weight, self.bias, self.running_mean, self.running_var, residual, relu, self.eps,
                                self.momentum, groups, grad_join)
         if not getattr(self, "_nbt_in_arena", False):
-            self.num_batches_tracked += groups   # else: one add per net per forward, see R21DBYOL.forward
+            self.num_batches_tracked += groups   # else: one add per net per forward, see ByolBase._two_view_step
         return y
 
     def relu_then(self, conv, x, groups=1, bn_groups=0, bn_pivot=None):
@@ -331,10 +331,10 @@ class R2Plus1DNet(nn.Module):
     # encoder's last stage, then conv5 .. conv2, then the stem
     GRAD_STAGES = ("head", "conv5", "conv4", "conv3", "conv2", "stem")
 
-    def forward(self, x, groups=1, after_conv2=None, stage_done=None):
+    def forward(self, x, groups=1, after_early_stage=None, stage_done=None):
         """``groups`` > 1: x holds that many independent forward calls back to back along the batch axis
         (BN statistics stay per call); convolutions are per-sample, so the result equals separate calls.
-        ``after_conv2``: called once the conv2 stage is enqueued (R21DBYOL starts the target network's stream there).
+        ``after_early_stage``: called once the conv2 stage is enqueued (R21DBYOL starts the target network's stream there).
         ``stage_done(i)``: called DURING BACKWARD when the gradient of stage i's input exists, i.e. when every parameter
         gradient of GRAD_STAGES[i] (and of the stages before it) has been enqueued -- the data-parallel step starts that
         slice's all-reduce there instead of after the whole backward pass (cstp_amd.train.StagedAllReduce)."""
@@ -344,8 +344,8 @@ class R2Plus1DNet(nn.Module):
             return t
         x = mark(self.bn1(self.conv1(x, groups), relu=True, groups=groups), 4)      # conv2's input: conv2 is complete
         x = mark(self.conv2(x, groups), 3)
-        if after_conv2 is not None:
-            after_conv2()
+        if after_early_stage is not None:
+            after_early_stage()
         x = mark(self.conv3(x, groups), 2)
         x = mark(self.conv4(x, groups), 1)
         x = mark(self.conv5(x, groups), 0)                                         # projector, predictor, heads are complete
@@ -356,11 +356,14 @@ class R2Plus1DNet(nn.Module):
 
 
 class ByolBase(nn.Module):
-    """What the BYOL wrappers of both backbones share (R21DBYOL here, R3DBYOL in r3d_byol.py): the Glorot re-initialisation,
-    the flat parameter / gradient / target arenas, the EMA and the regression loss.  Subclasses provide ``online_net``,
-    ``target_net`` (pretrain), ``pretrain`` and ``_head_bn_calls()``."""
+    """What the BYOL wrappers of the four backbones share (R21DBYOL here, R3DBYOL, S3DGBYOL and I3DBYOL in their modules): the
+    Glorot re-initialisation, the flat parameter / gradient / target arenas, the EMA, the regression loss and the two-view
+    training step (o_type 'loss_com').  Subclasses provide ``online_net``, ``target_net``, ``predictor`` and the four pretext
+    heads (pretrain), ``pretrain`` and ``_head_bn_calls()``."""
 
     _arenas = None
+    act_bf16 = False           # True: the clip pair is rounded to bf16 once (bf16 activation storage)
+    ROT_HEAD = "rotate_cls"    # attribute name of the rotation head (the reference's wrappers spell it two ways)
     _grad_stage_cb = None      # set by the data-parallel training step: called with a stage index during backward
 
     def grad_stage_slices(self):
@@ -555,6 +558,96 @@ class ByolBase(nn.Module):
     def _cal_loss(self, online_feat_1, online_feat_2, target_feat_1, target_feat_2):
         return self._loss_fn(online_feat_1, target_feat_2) + self._loss_fn(online_feat_2, target_feat_1)
 
+    def _normed_classify(self, feat, o_type, norm):
+        """The R3D / S3D-G fine-tune tail: classify(classify_bn(l2_normalize(feat))), the classifier alone when the model was
+        built without ``norm`` or o_type is 'scratch'."""
+        if norm and o_type != "scratch":
+            feat = self.classify_bn(ops.l2_normalize(feat))
+        out = self.classify(feat)
+        if self.training and self._arenas is not None:
+            self._arenas["nbt"]["all"] += 1
+            if norm and o_type == "scratch":
+                self.classify_bn.num_batches_tracked -= 1    # not called on the scratch branch
+        return out
+
+    @staticmethod
+    def _projection(out):
+        """The tensor the predictor, the target comparison and ``last_projections`` use: an encoder with a projector returns
+        (feature, projection), one without returns the feature alone."""
+        return out[1] if isinstance(out, tuple) else out
+
+    def _head(self, head, x):
+        """A two-view pretext head: the _MLP heads hold a BatchNorm and take the views as two groups, plain Linear heads do not."""
+        return head(x, groups=2) if isinstance(head, _MLP) else head(x)
+
+    def _two_view_step(self, x1, x2):
+        """o_type 'loss_com' of every wrapper: (loss_byol, (pred_spa, pred_tem, pred_pb_1, pred_pb_2, pred_rot_1, pred_rot_2))."""
+        if not self.pretrain:
+            raise AttributeError("%s(pretrain=False) has no target_net/predictor: o_type='loss_com' needs pretrain=True"
+                                 % type(self).__name__)
+        if x2 is None or x2.shape != x1.shape:
+            raise ValueError("o_type='loss_com' needs two clips of identical shape")
+        b = x1.shape[0]
+        # Both views go through ONE launch sequence per network as a batch of 2B with two BN groups:
+        # convolutions are per-sample and BN statistics stay per view, so this is the reference's
+        # online_net(x1); online_net(x2) (r21d_byol.py:359-360) with half the launches, one weight
+        # pack per layer and twice the grid on the small deep layers.
+        x = torch.cat((x1, x2), dim=0)
+        if self.act_bf16:
+            x = ops.to_bf16(x)             # bf16 storage: ops dispatch on the activation dtype from here on
+        tgt = {}
+
+        def target_pass():
+            with torch.no_grad():
+                self._update_target_net()                              # EMA BEFORE the target forward (:364)
+                t = self._projection(self.target_net(x, groups=2))     # train-mode BN, own running stats (:365-366)
+                tgt["swapped"] = torch.cat((t[b:], t[:b]), dim=0).detach()
+
+        kw = {"stage_done": self._grad_stage_cb} if hasattr(self.online_net, "GRAD_STAGES") else {}
+        overlap = OVERLAP_TARGET_FORWARD and x.is_cuda     # (the module's one switch, read per call: bench.py serialises with it)
+        if overlap:
+            # The target network's forward depends on nothing the online forward produces (the EMA reads the online
+            # PARAMETERS, which no forward modifies), so it runs on a second HIP stream: its HBM-bound BatchNorm kernels
+            # execute beside the other network's matrix-core-bound convolutions instead of alternating with them.
+            main = torch.cuda.current_stream(x.device)
+            side = self._side_stream(x.device)
+
+            def start_target():
+                # STAGGERED: the side stream starts once the online network's early stage (R(2+1)D: stem and conv2, the big 56x56
+                # layers, where the dominant kernel lives) is through, so those launches run alone -- their HIP-event timing stays
+                # the kernel's own duration -- and the target forward overlaps the online network's later stages and heads.
+                side.wait_stream(main)
+                with torch.cuda.stream(side):
+                    target_pass()
+
+            kw["after_early_stage"] = start_target
+        out = self.online_net(x, groups=2, **kw)
+        online_feat = out[0] if isinstance(out, tuple) else out
+        online_proj = self._projection(out)
+        online_pred = self.predictor(online_proj, groups=2)
+        if overlap:
+            main.wait_stream(side)
+            tgt["swapped"].record_stream(main)
+            x.record_stream(side)
+        else:
+            target_pass()
+        # loss_fn(pred_1, tproj_2) + loss_fn(pred_2, tproj_1)  (:351-355)
+        rows = self._loss_fn(online_pred, tgt["swapped"])
+        loss = rows[:b] + rows[b:]
+        feat_cat = torch.cat((online_feat[:b], online_feat[b:]), dim=1)
+        pred_spa = self.overlap_spa(feat_cat)
+        pred_tem = self.overlap_tem(feat_cat)
+        pred_pb = self._head(self.pb_cls, online_feat)
+        pred_rot = self._head(getattr(self, self.ROT_HEAD), online_feat)
+        if self._arenas is not None:   # BN num_batches_tracked: three adds instead of 108
+            nbt = self._arenas["nbt"]
+            nbt["online"] += 2
+            nbt["target"] += 2
+            nbt["heads"] += nbt["heads_inc"]
+        # kept for the NT-Xent head and for parity tests (no extra work)
+        self.last_projections = (online_proj[:b], online_proj[b:])
+        return loss.mean(), (pred_spa, pred_tem, pred_pb[:b], pred_pb[b:], pred_rot[:b], pred_rot[b:])
+
 
 class R21DBYOL(ByolBase):
     """forward(x1, x2, o_type='loss_com') -> (loss_byol, (pred_spa, pred_tem, pred_pb_1, pred_pb_2,
@@ -595,70 +688,7 @@ class R21DBYOL(ByolBase):
 
     def forward(self, x1, x2=None, o_type=None):
         if o_type == "loss_com":
-            if not self.pretrain:
-                raise AttributeError("R21DBYOL(pretrain=False) has no target_net/predictor: o_type='loss_com' needs "
-                                     "pretrain=True")
-            if x2 is None or x2.shape != x1.shape:
-                raise ValueError("o_type='loss_com' needs two clips of identical shape")
-            b = x1.shape[0]
-            # Both views go through ONE launch sequence per network as a batch of 2B with two BN groups:
-            # convolutions are per-sample and BN statistics stay per view, so this is the reference's
-            # online_net(x1); online_net(x2) (r21d_byol.py:359-360) with half the launches, one weight
-            # pack per layer and twice the grid on the small deep layers.
-            x = torch.cat((x1, x2), dim=0)
-            if self.act_bf16:
-                x = ops.to_bf16(x)             # bf16 storage: ops dispatch on the activation dtype from here on
-            if OVERLAP_TARGET_FORWARD and x.is_cuda:
-                # The target network's forward depends on nothing the online forward produces (the EMA reads the online
-                # PARAMETERS, which no forward modifies), so it runs on a second HIP stream: its HBM-bound BatchNorm kernels
-                # execute beside the other network's matrix-core-bound convolutions instead of alternating with them.
-                main = torch.cuda.current_stream(x.device)
-                side = self._side_stream(x.device)
-                tgt = {}
-
-                def start_target():
-                    # STAGGERED: the side stream starts once the online network's stem and conv2 stage (the big 56x56 layers,
-                    # where the dominant kernel lives) are through, so those launches run alone -- their HIP-event timing stays
-                    # the kernel's own duration -- and the target forward overlaps the online conv3..conv5 stages and heads.
-                    side.wait_stream(main)
-                    with torch.cuda.stream(side), torch.no_grad():
-                        self._update_target_net()              # EMA BEFORE the target forward (:364)
-                        _, target_proj = self.target_net(x, groups=2)
-                        tgt["swapped"] = torch.cat((target_proj[b:], target_proj[:b]), dim=0).detach()
-
-                online_feat, online_proj = self.online_net(x, groups=2, after_conv2=start_target,
-                                                           stage_done=self._grad_stage_cb)
-                online_pred = self.predictor(online_proj, groups=2)
-                main.wait_stream(side)
-                target_swapped = tgt["swapped"]
-                target_swapped.record_stream(main)
-                x.record_stream(side)
-            else:
-                online_feat, online_proj = self.online_net(x, groups=2, stage_done=self._grad_stage_cb)
-                online_pred = self.predictor(online_proj, groups=2)
-                with torch.no_grad():
-                    self._update_target_net()                      # EMA BEFORE the target forward (:364)
-                    _, target_proj = self.target_net(x, groups=2)  # train-mode BN, own running stats (:365-366)
-                    target_swapped = torch.cat((target_proj[b:], target_proj[:b]), dim=0).detach()
-            # loss_fn(pred_1, tproj_2) + loss_fn(pred_2, tproj_1)  (:351-355)
-            rows = self._loss_fn(online_pred, target_swapped)
-            loss = rows[:b] + rows[b:]
-            online_feat_1, online_feat_2 = online_feat[:b], online_feat[b:]
-            feat_cat = torch.cat((online_feat_1, online_feat_2), dim=1)
-            pred_spa = self.overlap_spa(feat_cat)
-            pred_tem = self.overlap_tem(feat_cat)
-            pred_pb = self.pb_cls(online_feat, groups=2)
-            pred_rot = self.rotate_cls(online_feat, groups=2)
-            pred_pb_1, pred_pb_2 = pred_pb[:b], pred_pb[b:]
-            pred_rot_1, pred_rot_2 = pred_rot[:b], pred_rot[b:]
-            if self._arenas is not None:   # BN num_batches_tracked: three adds instead of 108
-                nbt = self._arenas["nbt"]
-                nbt["online"] += 2
-                nbt["target"] += 2
-                nbt["heads"] += nbt["heads_inc"]
-            # kept for the NT-Xent head and for parity tests (no extra work)
-            self.last_projections = (online_proj[:b], online_proj[b:])
-            return loss.mean(), (pred_spa, pred_tem, pred_pb_1, pred_pb_2, pred_rot_1, pred_rot_2)
+            return self._two_view_step(x1, x2)
         elif o_type == "r_byol":
             raise NotImplementedError("o_type='r_byol' is shape-broken in the reference (predictor fed a tuple, "
                                       "r21d_byol.py:384-385); use o_type='loss_com'")

@@ -38,7 +38,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .r21d_byol import (OVERLAP_TARGET_FORWARD, BatchNorm1d, BatchNorm3d, ByolBase, Conv3d, Linear, Predictor, ReLU,  # noqa: F401
+from .r21d_byol import (BatchNorm1d, BatchNorm3d, ByolBase, Conv3d, Linear, Predictor, ReLU,  # noqa: F401
                         get_fine_tuning_parameters)
 
 LAYERS = {10: (1, 1, 1, 1), 18: (2, 2, 2, 2), 34: (3, 4, 6, 3)}
@@ -154,15 +154,15 @@ class ResNet(nn.Module):
             layers.append(block(self.inplanes, planes))
         return _Stage(*layers)
 
-    def forward(self, x, groups=1, after_layer1=None):
+    def forward(self, x, groups=1, after_early_stage=None):
         """``groups`` > 1: x holds that many independent forward calls back to back along the batch axis (per-call BN
         statistics); convolutions and pooling are per-sample, so the result equals separate calls.
-        ``after_layer1``: called once layer1 is enqueued (R3DBYOL starts the target network's stream there)."""
+        ``after_early_stage``: called once layer1 is enqueued (R3DBYOL starts the target network's stream there)."""
         x = self.bn1(self.conv1(x), relu=True, groups=groups)
         x = ops.max_pool3d(x, 3, 2, 1)
         x = self.layer1(x, groups)
-        if after_layer1 is not None:
-            after_layer1()
+        if after_early_stage is not None:
+            after_early_stage()
         x = self.layer2(x, groups)
         x = self.layer3(x, groups)
         x = self.layer4(x, groups)
@@ -196,6 +196,7 @@ def resnet50(**kwargs):
 class R3DBYOL(ByolBase):
     """forward(x1, x2, o_type='loss_com') -> (loss_byol, (pred_spa, pred_tem, pred_pb_1, pred_pb_2, pred_rot_1, pred_rot_2))
     with [B,5], [B,5], [B,4] x4 logits (r3d_byol.py:381-405)."""
+    ROT_HEAD = "rot_cls"      # the rotation head's attribute name in this wrapper
 
     def __init__(self, momentum=0.996, pretrain=True, cls_bn=False, opts=None):
         super().__init__()
@@ -232,55 +233,7 @@ class R3DBYOL(ByolBase):
 
     def forward(self, x1, x2=None, o_type="r_byol"):
         if o_type == "loss_com":
-            if not self.pretrain:
-                raise AttributeError("R3DBYOL(pretrain=False) has no target_net/predictor: o_type='loss_com' needs pretrain=True")
-            if x2 is None or x2.shape != x1.shape:
-                raise ValueError("o_type='loss_com' needs two clips of identical shape")
-            b = x1.shape[0]
-            x = torch.cat((x1, x2), dim=0)     # both views through one launch sequence, per-view BN statistics (groups=2)
-            if self.act_bf16:
-                x = ops.to_bf16(x)             # bf16 storage: ops dispatch on the activation dtype from here on
-            if OVERLAP_TARGET_FORWARD and x.is_cuda:
-                # target forward on a second HIP stream, staggered behind the online stem + layer1 (see R21DBYOL.forward)
-                main = torch.cuda.current_stream(x.device)
-                side = self._side_stream(x.device)
-                tgt = {}
-
-                def start_target():
-                    side.wait_stream(main)
-                    with torch.cuda.stream(side), torch.no_grad():
-                        self._update_target_net()             # EMA BEFORE the target forward (:388)
-                        target_feat = self.target_net(x, groups=2)
-                        tgt["swapped"] = torch.cat((target_feat[b:], target_feat[:b]), dim=0).detach()
-
-                online_feat = self.online_net(x, groups=2, after_layer1=start_target)
-                online_pred = self.predictor(online_feat, groups=2)
-                main.wait_stream(side)
-                target_swapped = tgt["swapped"]
-                target_swapped.record_stream(main)
-                x.record_stream(side)
-            else:
-                online_feat = self.online_net(x, groups=2)
-                online_pred = self.predictor(online_feat, groups=2)
-                with torch.no_grad():
-                    self._update_target_net()                     # EMA BEFORE the target forward (:388)
-                    target_feat = self.target_net(x, groups=2)
-                    target_swapped = torch.cat((target_feat[b:], target_feat[:b]), dim=0).detach()
-            rows = self._loss_fn(online_pred, target_swapped)   # loss_fn(pred_1, t_2) + loss_fn(t_1, pred_2)  (:317-321)
-            loss = rows[:b] + rows[b:]
-            f1, f2 = online_feat[:b], online_feat[b:]
-            feat_cat = torch.cat((f1, f2), dim=1)
-            pred_spa = self.overlap_spa(feat_cat)
-            pred_tem = self.overlap_tem(feat_cat)
-            pred_pb = self.pb_cls(online_feat)
-            pred_rot = self.rot_cls(online_feat)
-            if self._arenas is not None:
-                nbt = self._arenas["nbt"]
-                nbt["online"] += 2
-                nbt["target"] += 2
-                nbt["heads"] += nbt["heads_inc"]
-            self.last_projections = (online_feat[:b], online_feat[b:])   # NT-Xent head input (no projector in this wrapper)
-            return loss.mean(), (pred_spa, pred_tem, pred_pb[:b], pred_pb[b:], pred_rot[:b], pred_rot[b:])
+            return self._two_view_step(x1, x2)
         if o_type == "r_byol":
             raise NotImplementedError("o_type='r_byol' reads an attribute the reference never sets (self.shuffle_bn, "
                                       "r3d_byol.py:410); use o_type='loss_com'")
@@ -288,13 +241,5 @@ class R3DBYOL(ByolBase):
             if self.pretrain:
                 raise AttributeError("R3DBYOL(pretrain=True) has no classify: o_type=%r needs pretrain=False" % o_type)
             online_feat = self.online_net(ops.to_bf16(x1) if self.act_bf16 else x1)     # pooled features are fp32 either way
-            if o_type != "scratch" and self.cls_bn:             # :420-428 vs :429-432
-                online_feat = ops.l2_normalize(online_feat)
-                online_feat = self.classify_bn(online_feat)
-            out = self.classify(online_feat)
-            if self.training and self._arenas is not None:
-                self._arenas["nbt"]["all"] += 1
-                if self.cls_bn and o_type == "scratch":
-                    self.classify_bn.num_batches_tracked -= 1    # not called on the scratch branch (:429-432)
-            return out
+            return self._normed_classify(online_feat, o_type, self.cls_bn)              # :420-428 vs :429-432
         return None     # the reference falls off the end of forward for any other o_type

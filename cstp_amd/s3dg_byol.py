@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .r21d_byol import (OVERLAP_TARGET_FORWARD, BatchNorm1d, BatchNorm3d, ByolBase, Conv3d, Linear, Predictor, Projector, ReLU,
+from .r21d_byol import (BatchNorm1d, BatchNorm3d, ByolBase, Conv3d, Linear, Predictor, Projector, ReLU,
                         _MLP)
 
 # A/B switch: 0 = self-gating and the inception concat composed from ops.linear + ATen mean / sigmoid / mul / cat
@@ -221,14 +221,14 @@ class S3D(nn.Module):
                 raise ValueError("clip %s is too small for S3D-G: its stem and four max-poolings reduce it to nothing "
                                  "(needs at least 5 frames of 17x17 pixels)" % (tuple(shape[1:]),))
 
-    def forward(self, x, groups=1, after_block2=None):
+    def forward(self, x, groups=1, after_early_stage=None):
         """``groups`` > 1: x holds that many independent forward calls back to back along the batch axis (per-call BN
-        statistics).  ``after_block2``: called once block2 is enqueued (S3DGBYOL starts the target network's stream there)."""
+        statistics).  ``after_early_stage``: called once block2 is enqueued (S3DGBYOL starts the target network's stream there)."""
         self.check_clip(x.shape)
         x = self.Conv_1a(x, groups)
         x = self.Conv_2c(self.Conv_2b(self.MaxPool_2a(x), groups), groups)
-        if after_block2 is not None:
-            after_block2()
+        if after_early_stage is not None:
+            after_early_stage()
         x = self.MaxPool_3a(x)
         for m in (self.Mixed_3b, self.Mixed_3c):
             x = m(x, groups)
@@ -285,68 +285,12 @@ class S3DGBYOL(ByolBase):
 
     def forward(self, x1, x2=None, o_type="r_byol"):
         if o_type == "loss_com":
-            if not self.pretrain:
-                raise AttributeError("S3DGBYOL(pretrain=False) has no target_net/predictor: o_type='loss_com' needs pretrain=True")
-            if x2 is None or x2.shape != x1.shape:
-                raise ValueError("o_type='loss_com' needs two clips of identical shape")
-            b = x1.shape[0]
-            # both views through one launch sequence per network, per-view BN statistics (groups=2): the reference's
-            # online_net(x1); online_net(x2) (:489-490)
-            x = torch.cat((x1, x2), dim=0)
-            if OVERLAP_TARGET_FORWARD and x.is_cuda:
-                # target forward on a second HIP stream, staggered behind the online block1 + block2 (see R21DBYOL.forward)
-                main = torch.cuda.current_stream(x.device)
-                side = self._side_stream(x.device)
-                tgt = {}
-
-                def start_target():
-                    side.wait_stream(main)
-                    with torch.cuda.stream(side), torch.no_grad():
-                        self._update_target_net()             # EMA BEFORE the target forward (:493)
-                        _, target_proj = self.target_net(x, groups=2)
-                        tgt["swapped"] = torch.cat((target_proj[b:], target_proj[:b]), dim=0).detach()
-
-                online_feat, online_proj = self.online_net(x, groups=2, after_block2=start_target)
-                online_pred = self.predictor(online_proj, groups=2)
-                main.wait_stream(side)
-                target_swapped = tgt["swapped"]
-                target_swapped.record_stream(main)
-                x.record_stream(side)
-            else:
-                online_feat, online_proj = self.online_net(x, groups=2)
-                online_pred = self.predictor(online_proj, groups=2)
-                with torch.no_grad():
-                    self._update_target_net()                     # EMA BEFORE the target forward (:493)
-                    _, target_proj = self.target_net(x, groups=2)
-                    target_swapped = torch.cat((target_proj[b:], target_proj[:b]), dim=0).detach()
-            rows = self._loss_fn(online_pred, target_swapped)     # loss_fn(p1, t2) + loss_fn(t1, p2)  (:421-425)
-            loss = rows[:b] + rows[b:]
-            feat_cat = torch.cat((online_feat[:b], online_feat[b:]), dim=1)
-            pred_spa = self.overlap_spa(feat_cat)
-            pred_tem = self.overlap_tem(feat_cat)
-            pred_pb = self.pb_cls(online_feat, groups=2)
-            pred_rot = self.rotate_cls(online_feat, groups=2)
-            if self._arenas is not None:
-                nbt = self._arenas["nbt"]
-                nbt["online"] += 2
-                nbt["target"] += 2
-                nbt["heads"] += nbt["heads_inc"]
-            self.last_projections = (online_proj[:b], online_proj[b:])   # NT-Xent head input, as in R(2+1)D
-            return loss.mean(), (pred_spa, pred_tem, pred_pb[:b], pred_pb[b:], pred_rot[:b], pred_rot[b:])
+            return self._two_view_step(x1, x2)
         if o_type == "r_byol":
             raise NotImplementedError("o_type='r_byol' is shape-broken in the reference (the predictor is fed the (feature, "
                                       "projection) tuple, s3dg.py:514-518); use o_type='loss_com'")
         if o_type in ["ft_fc", "ft_all", "test", "scratch"]:
             if self.pretrain:
                 raise AttributeError("S3DGBYOL(pretrain=True) has no classify: o_type=%r needs pretrain=False" % o_type)
-            online_feat = self.online_net(x1)
-            if o_type != "scratch" and self.l2_norm:              # :526-534 vs :535-538
-                online_feat = ops.l2_normalize(online_feat)
-                online_feat = self.classify_bn(online_feat)
-            out = self.classify(online_feat)
-            if self.training and self._arenas is not None:
-                self._arenas["nbt"]["all"] += 1
-                if self.l2_norm and o_type == "scratch":
-                    self.classify_bn.num_batches_tracked -= 1    # not called on the scratch branch
-            return out
+            return self._normed_classify(self.online_net(x1), o_type, self.l2_norm)     # :526-534 vs :535-538
         return None     # the reference falls off the end of forward for any other o_type

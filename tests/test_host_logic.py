@@ -148,3 +148,16 @@ def test_synthetic_dataset_label_ranges():
     assert 0 <= spa < 5 and 0 <= tem < 5 and 0 <= pb < 4 and 0 <= r1 < 4 and 0 <= r2 < 4
     (d1, _), _ = ds[3]
     assert torch.equal(c1, d1) and not torch.equal(c1, c2)
+
+
+def test_one_two_view_step_and_one_overlap_switch():
+    """The four BYOL wrappers share ByolBase's two-view step, and the target-forward overlap has ONE switch
+    (r21d_byol.OVERLAP_TARGET_FORWARD, read per call): the other backbone modules hold no copy of it."""
+    from cstp_amd import i3d_byol, r21d_byol, r3d_byol, s3dg_byol
+    assert isinstance(r21d_byol.OVERLAP_TARGET_FORWARD, bool)
+    for mod in (r3d_byol, s3dg_byol, i3d_byol):
+        assert not hasattr(mod, "OVERLAP_TARGET_FORWARD"), mod.__name__
+    base = r21d_byol.ByolBase
+    for cls in (r21d_byol.R21DBYOL, r3d_byol.R3DBYOL, s3dg_byol.S3DGBYOL, i3d_byol.I3DBYOL):
+        assert issubclass(cls, base) and "_two_view_step" not in vars(cls)
+        assert cls._two_view_step is base._two_view_step

@@ -387,8 +387,15 @@ def _tol(base, dev):
     return max(base, HIP_VS_FP32 * float(dev))
 
 
-@pytest.mark.parametrize("name", ["i3d_small", "i3d_112"])
-def test_i3d_pretrain_matches_reference_golden(name):
+# the smallest case also runs with the target forward on the main stream (ByolBase._two_view_step's serial branch); the ids of
+# the existing cases are unchanged
+GOLDEN_CASES = ["i3d_small", "i3d_112"]
+@pytest.mark.parametrize("name,overlap", [pytest.param(n, True if n == "i3d_small" else None, id=n) for n in GOLDEN_CASES]
+                         + [pytest.param("i3d_small", False, id="i3d_small-serial")])
+def test_i3d_pretrain_matches_reference_golden(name, overlap, monkeypatch):
+    if overlap is not None:
+        from cstp_amd import r21d_byol
+        monkeypatch.setattr(r21d_byol, "OVERLAP_TARGET_FORWARD", overlap)
     from cstp_amd.optim import FlatSGD
     from cstp_amd.train import PretrainStep
     from oracle import r21d_byol_oracle as orc

@@ -65,13 +65,19 @@ def momentum_checksums(opt):
                      if i in sd else [0.0, 0.0] for i in range(n)])
 
 
-@pytest.mark.parametrize("name", ["d1_small", "r18_small", "r34_small", "d1_cfg1", "r18_cfg2", "d1_heavy", "r18_heavy",
-                                  "r34_heavy", "r34_cfg4"])
-def test_hip_path_matches_reference_golden(name):
+# the smallest case also runs with the target forward on the main stream (ByolBase._two_view_step's serial branch); the ids of
+# the existing cases are unchanged
+GOLDEN_CASES = ["d1_small", "r18_small", "r34_small", "d1_cfg1", "r18_cfg2", "d1_heavy", "r18_heavy", "r34_heavy", "r34_cfg4"]
+@pytest.mark.parametrize("name,overlap", [pytest.param(n, True if n == "d1_small" else None, id=n) for n in GOLDEN_CASES]
+                         + [pytest.param("d1_small", False, id="d1_small-serial")])
+def test_hip_path_matches_reference_golden(name, overlap, monkeypatch):
     """``*_heavy``: magnitudes inside every weight tensor and inside the clips span six decades (2^0 .. 2^-20 per element,
     half of the pixels zero) -- the default 2xf16-split GEMM arithmetic, with its ONE power-of-two scale per activation
     tensor, has to hold the same 1e-4 bar there.  ``r34_cfg4``: BASELINE configs[3]'s true clip shape (R(2+1)D-34, 32
     frames of 112x112)."""
+    if overlap is not None:
+        from cstp_amd import r21d_byol
+        monkeypatch.setattr(r21d_byol, "OVERLAP_TARGET_FORWARD", overlap)
     from cstp_amd.optim import FlatSGD
     from oracle import r21d_byol_oracle as orc
     g = load(name)

@@ -201,6 +201,75 @@ def test_bn_relu_conv3d_fused(xs, k, ks, st, pd, groups):
     assert rel_err(gg.grad, gamma.grad) < TOL and rel_err(bg.grad, beta.grad) < TOL
 
 
+def _wgrad_case(op):
+    """(forward(w) -> y on the GPU, dy on the GPU, the fp32 weight, its ATen fp64 gradient on the CPU, the bar of that op's own test)"""
+    from cstp_amd import ops
+    if op == "conv3d_bf16":     # the smallest geometry of test_b16_gpu.test_conv3d_bf16_forward_backward, its operands and its bar
+        xs, k, ks, st, pd = (1, 48, 2, 4, 8), 32, (3, 3, 3), (1, 1, 1), (1, 1, 1)
+        g = torch.Generator().manual_seed(sum(xs) + k)
+        x = torch.randn(xs, generator=g).to(torch.bfloat16)
+        w = torch.randn((k, xs[1]) + ks, generator=g) / (xs[1] * 27) ** 0.5
+        w64 = w.to(torch.bfloat16).double().requires_grad_(True)
+        y = F.conv3d(x.double(), w64, None, st, pd)
+        dy = torch.randn(y.shape, generator=g).to(torch.bfloat16)
+        y.backward(dy.double())
+        xg = x.cuda().requires_grad_(True)
+        return (lambda wg: ops.conv3d(xg, wg, None, st, pd)), dy.cuda(), w, w64.grad, 2e-5
+    if op == "conv3d":
+        n, c, d, h, wd, k, ks, st, pd = CONVS[1]
+        x = _rand((n, c, d, h, wd), 1)
+        w = (_rand((k, c) + ks, 2) * 0.2).requires_grad_(True)
+        y = F.conv3d(x, w, None, st, pd)
+        dy = _rand(tuple(y.shape), 3)
+        y.backward(dy)
+        xg = x.float().cuda().requires_grad_(True)
+        return (lambda wg: ops.conv3d(xg, wg, None, st, pd)), dy.float().cuda(), w.detach().float(), w.grad, TOL
+    xs, k, ks, st, pd, groups = min(FUSED, key=lambda f: f[0][0] * f[0][1] * f[0][2] * f[0][3] * f[0][4])
+    c, half = xs[1], xs[0] // groups
+    x = _rand(xs, 41) * 1.3 + 0.2
+    gamma, beta = _rand((c,), 42), _rand((c,), 43) * 0.2
+    w = (_rand((k, c) + ks, 44) * 0.1).requires_grad_(True)
+    rm, rv = torch.zeros(c, dtype=torch.float64), torch.ones(c, dtype=torch.float64)
+    zs = [F.relu(F.batch_norm(x[i * half:(i + 1) * half], rm, rv, gamma, beta, True, 0.1, 1e-5)) for i in range(groups)]
+    y = F.conv3d(torch.cat(zs, 0), w, None, st, pd)
+    dy = _rand(tuple(y.shape), 45)
+    y.backward(dy)
+    xg, gg, bg = x.float().cuda().requires_grad_(True), gamma.float().cuda(), beta.float().cuda()
+
+    def fwd(wg):
+        return ops.bn_relu_conv3d(xg, gg, bg, torch.zeros(c, device="cuda"), torch.ones(c, device="cuda"), wg, st, pd,
+                                  groups=groups, relu=True)
+    return fwd, dy.float().cuda(), w.detach().float(), w.grad, TOL
+
+
+@pytest.mark.parametrize("op", ["conv3d", "bn_relu_conv3d", "conv3d_bf16"])
+def test_weight_gradient_placement(op, monkeypatch):
+    """The three places a convolution's weight gradient can go (ops._place_wgrad) hold the same numbers: (a) a fresh tensor
+    handed to autograd; added by the kernel into an existing .grad, autograd handed None, (b) on the launch stream and (c) on
+    the side stream.  Each against ATen's fp64 gradient at the bar of the op's own forward/backward test."""
+    from cstp_amd import ops
+    fwd, dy, w0, dw_ref, tol = _wgrad_case(op)
+    w = w0.cuda().requires_grad_(True)
+    fwd(w).backward(dy)
+    torch.cuda.synchronize()
+    err = rel_err(w.grad, dw_ref)
+    print("%s fresh: %.3g (bar %g)" % (op, err, tol))
+    assert err < tol
+    g0 = (_rand(tuple(w0.shape), 7) * dw_ref.abs().max()).float()      # an existing gradient of the new one's magnitude
+    for overlap in (False, True):
+        monkeypatch.setattr(ops, "OVERLAP_WGRAD", overlap)
+        w = w0.cuda().requires_grad_(True)
+        w.grad = held = g0.cuda()
+        w._cstp_direct_grad = True
+        fwd(w).backward(dy)
+        ops._join_side_streams()
+        torch.cuda.synchronize()
+        assert w.grad is held               # autograd was handed None: a returned gradient would have been added a second time
+        err = rel_err(w.grad.double().cpu() - g0.double(), dw_ref)
+        print("%s direct, side stream %s: %.3g (bar %g)" % (op, overlap, err, tol))
+        assert err < tol
+
+
 def test_bn_rejects_single_value():
     from cstp_amd import ops, _lib
     x = torch.ones(1, 8, device="cuda")

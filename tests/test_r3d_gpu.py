@@ -42,8 +42,15 @@ def _opts(depth, t, hw, k=101):
     return argparse.Namespace(model_depth=depth, sample_size=hw, sample_duration=t, sc_type="B", n_classes=k)
 
 
-@pytest.mark.parametrize("name", ["r3d_10_small", "r3d_18_small", "r3d_34_small"])
-def test_r3d_hip_matches_reference_golden(name):
+# the smallest case also runs with the target forward on the main stream (ByolBase._two_view_step's serial branch); the ids of
+# the existing cases are unchanged
+GOLDEN_CASES = ["r3d_10_small", "r3d_18_small", "r3d_34_small"]
+@pytest.mark.parametrize("name,overlap", [pytest.param(n, True if n == "r3d_10_small" else None, id=n) for n in GOLDEN_CASES]
+                         + [pytest.param("r3d_10_small", False, id="r3d_10_small-serial")])
+def test_r3d_hip_matches_reference_golden(name, overlap, monkeypatch):
+    if overlap is not None:
+        from cstp_amd import r21d_byol
+        monkeypatch.setattr(r21d_byol, "OVERLAP_TARGET_FORWARD", overlap)
     from cstp_amd import ops
     from cstp_amd.optim import FlatSGD
     from cstp_amd.r3d_byol import R3DBYOL

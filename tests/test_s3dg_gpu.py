@@ -146,8 +146,15 @@ def _tol(base, dev):
     return max(base, HIP_VS_FP32 * float(dev))
 
 
-@pytest.mark.parametrize("name", ["s3dg_small", "s3dg_112"])
-def test_s3dg_pretrain_matches_reference_golden(name):
+# the smallest case also runs with the target forward on the main stream (ByolBase._two_view_step's serial branch); the ids of
+# the existing cases are unchanged
+GOLDEN_CASES = ["s3dg_small", "s3dg_112"]
+@pytest.mark.parametrize("name,overlap", [pytest.param(n, True if n == "s3dg_small" else None, id=n) for n in GOLDEN_CASES]
+                         + [pytest.param("s3dg_small", False, id="s3dg_small-serial")])
+def test_s3dg_pretrain_matches_reference_golden(name, overlap, monkeypatch):
+    if overlap is not None:
+        from cstp_amd import r21d_byol
+        monkeypatch.setattr(r21d_byol, "OVERLAP_TARGET_FORWARD", overlap)
     from cstp_amd.optim import FlatSGD
     from cstp_amd.train import PretrainStep
     from oracle import r21d_byol_oracle as orc

@@ -115,30 +115,19 @@ def main():
     ms = (time.perf_counter() - t0) / a.steps * 1e3
 
     # ---- per-class roofline table: two more steps, stream overlaps off, every spanned call under a HIP-event pair
-    from cstp_amd import ops, r3d_byol as _r3d
+    from cstp_amd import ops, r21d_byol as _rb
     tm = AllTimers()
     ops.kernel_timer = tm
-    saved = (ops.OVERLAP_WGRAD, getattr(_r3d, "OVERLAP_TARGET_FORWARD", None))
+    saved = (ops.OVERLAP_WGRAD, _rb.OVERLAP_TARGET_FORWARD)
     ops.OVERLAP_WGRAD = False
-    if saved[1] is not None:
-        _r3d.OVERLAP_TARGET_FORWARD = False
-    try:
-        from cstp_amd import r21d_byol as _rb
-        rb_saved = _rb.OVERLAP_TARGET_FORWARD
-        _rb.OVERLAP_TARGET_FORWARD = False
-    except Exception:
-        _rb, rb_saved = None, None
+    _rb.OVERLAP_TARGET_FORWARD = False
     tm.enabled = True
     nrep = 2
     run(nrep)
     torch.cuda.synchronize()
     tm.enabled = False
     ops.kernel_timer = None
-    ops.OVERLAP_WGRAD = saved[0]
-    if saved[1] is not None:
-        _r3d.OVERLAP_TARGET_FORWARD = saved[1]
-    if _rb is not None:
-        _rb.OVERLAP_TARGET_FORWARD = rb_saved
+    ops.OVERLAP_WGRAD, _rb.OVERLAP_TARGET_FORWARD = saved
     classes = {}
     for (what, key), pairs in tm.pairs.items():
         name, flop, nbytes = classify(what, key)

@@ -71,17 +71,16 @@ def main():
     # ---- per-class table: two more steps, stream overlaps off, every spanned call under a HIP-event pair
     tm = AllTimers()
     ops.kernel_timer = tm
-    saved = (ops.OVERLAP_WGRAD, _rb.OVERLAP_TARGET_FORWARD, s3dg_byol.OVERLAP_TARGET_FORWARD)
+    saved = (ops.OVERLAP_WGRAD, _rb.OVERLAP_TARGET_FORWARD)
     ops.OVERLAP_WGRAD = False
     _rb.OVERLAP_TARGET_FORWARD = False
-    s3dg_byol.OVERLAP_TARGET_FORWARD = False
     tm.enabled = True
     nrep = 2
     run(nrep)
     torch.cuda.synchronize()
     tm.enabled = False
     ops.kernel_timer = None
-    ops.OVERLAP_WGRAD, _rb.OVERLAP_TARGET_FORWARD, s3dg_byol.OVERLAP_TARGET_FORWARD = saved
+    ops.OVERLAP_WGRAD, _rb.OVERLAP_TARGET_FORWARD = saved
     classes = {}
     for (what, key), pairs in tm.pairs.items():
         c = classes.setdefault(kernel_class(what, key), {"calls": 0, "ms": 0.0})
