@@ -761,37 +761,35 @@ static inline int tile_bn(const Tile& t) {   // split: wm = 128-column halves
 static inline bool patch_mt_ok(int mt) { return mt == 4 || mt == 8 || mt == 9; }
 static bool native_only();
 static int split_planes();
-// the patch kernel serves 1x3x3, stride 1, padding (0,1,1) in the f16-pair arithmetic, frames whose patch fits its LDS image
+// what the four LDS-resident kernels below ask of a layer: the spatial (1x3x3, padding (0,1,1)) or the temporal (3x1x1, padding
+// (1,0,0)) taps at stride 1, the f16-pair arithmetic, at least one 16-channel group on both sides
+static bool taps_133(const cstp_conv_desc& d) {
+  return d.kt == 1 && d.kh == 3 && d.kw == 3 && d.st == 1 && d.sh == 1 && d.sw == 1 && d.pt == 0 && d.ph == 1 && d.pw == 1;
+}
+static bool taps_311(const cstp_conv_desc& d) {
+  return d.kt == 3 && d.kh == 1 && d.kw == 1 && d.st == 1 && d.sh == 1 && d.sw == 1 && d.pt == 1 && d.ph == 0 && d.pw == 0;
+}
+static bool f16_pair_16ch(const cstp_conv_desc& d) { return !native_only() && split_planes() == 2 && d.c >= 16 && d.k >= 16; }
+// the patch kernel igemm_k1p (igemm_patch.h): the spatial layers whose frames' patch fits its LDS image
 static bool patch_geom_ok(const cstp_conv_desc& d) {
-  if (!(d.kt == 1 && d.kh == 3 && d.kw == 3 && d.st == 1 && d.sh == 1 && d.sw == 1 && d.pt == 0 && d.ph == 1 && d.pw == 1))
-    return false;
-  if (native_only() || split_planes() != 2 || d.c < 16 || d.k < 16) return false;
-  return patch_rows_needed(d.n * d.d, d.h, d.w) <= KP_ROWS;
+  return taps_133(d) && f16_pair_16ch(d) && patch_rows_needed(d.n * d.d, d.h, d.w) <= KP_ROWS;
 }
-// the temporal patch kernel igemm_k1t (igemm_tpatch.h): 3x1x1, stride 1, padding (1,0,0), f16 pair; tiles of 8 frames x 28
-// columns without remainder, whole 16-channel groups on both sides (the data gradient gathers the output channels)
+// the temporal patch kernel igemm_k1t (igemm_tpatch.h): tiles of 8 frames x 28 columns without remainder, whole 16-channel
+// groups on both sides (the data gradient gathers the output channels)
 static bool tpatch_geom_ok(const cstp_conv_desc& d) {
-  if (!(d.kt == 3 && d.kh == 1 && d.kw == 1 && d.st == 1 && d.sh == 1 && d.sw == 1 && d.pt == 1 && d.ph == 0 && d.pw == 0))
-    return false;
-  if (native_only() || split_planes() != 2 || d.c < 16 || d.k < 16 || (d.c & 15) != 0 || (d.k & 15) != 0) return false;
-  return d.d % KT_DT == 0 && (d.h * d.w) % KT_WT == 0;
+  return taps_311(d) && f16_pair_16ch(d) && (d.c & 15) == 0 && (d.k & 15) == 0 && d.d % KT_DT == 0 && (d.h * d.w) % KT_WT == 0;
 }
-// the weight-gradient patch kernel igemm_k2p (igemm_wpatch.h): the same layers; its x staging leads by <= 5 intervals of 64 rows
+// the weight-gradient patch kernel igemm_k2p (igemm_wpatch.h): the spatial layers; its x staging leads by <= 5 intervals of 64 rows
 static bool wpatch_geom_ok(const cstp_conv_desc& d) {
-  if (!(d.kt == 1 && d.kh == 3 && d.kw == 3 && d.st == 1 && d.sh == 1 && d.sw == 1 && d.pt == 0 && d.ph == 1 && d.pw == 1))
-    return false;
-  if (native_only() || split_planes() != 2 || d.c < 16 || d.k < 16) return false;
+  if (!taps_133(d) || !f16_pair_16ch(d)) return false;
   // (stream rows and frame counts stay below 2^25 and the divisors below 129: the kernel divides by multiplication)
   if ((long)d.n * d.d * (d.h + 1) * (d.w + 2) >= (1l << 25) || d.h + 1 > 128 || d.d > 128) return false;
   return 2 * (d.w + 2) + 66 <= 5 * 64;
 }
-// the temporal weight-gradient kernel igemm_k2t (igemm_wtpatch.h): 3x1x1, stride 1, padding (1,0,0), f16 pair, frames of whole
-// 32-position chunks (one aligned 128-byte line per channel, frame and chunk); item / frame-line counts below 2^26 (the kernel
-// divides by multiplication)
+// the temporal weight-gradient kernel igemm_k2t (igemm_wtpatch.h): frames of whole 32-position chunks (one aligned 128-byte line
+// per channel, frame and chunk); item / frame-line counts below 2^26 (the kernel divides by multiplication)
 static bool twpatch_geom_ok(const cstp_conv_desc& d) {
-  if (!(d.kt == 3 && d.kh == 1 && d.kw == 1 && d.st == 1 && d.sh == 1 && d.sw == 1 && d.pt == 1 && d.ph == 0 && d.pw == 0))
-    return false;
-  if (native_only() || split_planes() != 2 || d.c < 16 || d.k < 16) return false;
+  if (!taps_311(d) || !f16_pair_16ch(d)) return false;
   if ((d.h * d.w) % 16 != 0 || d.d > 255) return false;      // chunks of 32 positions, or of 16 (28 x 28 frames)
   // one chunk per frame serves one clip only: the item -> (clip, chunk) division multiplies by ceil(2^32 / chunks), which does not
   // fit in 32 bits for ONE chunk, so every item would land on clip 0 (S3D-G's Mixed_3b/3c on 4 x 4 frames, 8 x 32 x 32 clips)
@@ -871,23 +869,17 @@ static bool lookup_tuned(const cstp_conv_desc& d, int mode, Tile& t) {
   return true;
 }
 
+// what the descriptor alone fixes: output extents, operand padding, the size limits of the split kernels
 struct ConvPlan {
   int Do, Ho, Wo, ntaps;
-  // forward
-  Tile f_t; int f_Cp, f_Mp, f_Kp; bool f_straddle;
-  // dgrad
-  Tile d_t; int d_Cp, d_Mp, d_Kp;
-  // wgrad
-  int w_mt, w_blocks, w_Cp, w_Jtot, w_Jp; bool w_straddle; bool w_split; bool w_patch; bool w_tpatch;
+  bool straddle;             // the < 8-channel (stem) layers: channels not padded, a K tile straddles taps
+  bool x_small, y_small;     // the split kernels address their operands with 31-bit buffer offsets (bit 31 = "masked")
+  int f_Cp, f_Kp;            // forward: M = k, gather channels = c
+  int d_Cp, d_Kp;            // dgrad: M = c, gather channels = k
+  int w_Cp, w_Jtot, w_Jp;    // wgrad: M = k, J = (tap, c)
 };
 
-// with_affine: the plan of a FORWARD call that carries an input transform (cstp_in_affine: the BatchNorm + ReLU in front applied in
-// the kernel's staging).  The tuner times plain forwards, where the gather kernel igemm_k1s wins the 64-row temporal layers of the
-// first stage (0.40 ms against 0.48 for igemm_k1w); WITH the transform the gather kernel pays it once per filter tap and cannot
-// leave the next BatchNorm's sums (0.524 ms + 0.075 ms of bn_reduce against 0.523 ms, sums included; same-box step A/B 56.57 ->
-// 55.97 ms, profiles/r04).  So such a call runs the weight-resident kernel wherever it applies (CSTP_K1W=0: the tuner's tile).
-static bool k1w_preferred(const cstp_conv_desc& d, const Tile& t);
-static bool make_plan(const cstp_conv_desc& d, ConvPlan& p, bool with_affine = false) {
+static bool make_plan(const cstp_conv_desc& d, ConvPlan& p) {
   if (d.n <= 0 || d.c <= 0 || d.k <= 0 || d.d <= 0 || d.h <= 0 || d.w <= 0) return false;
   if (d.kt <= 0 || d.kh <= 0 || d.kw <= 0 || d.st <= 0 || d.sh <= 0 || d.sw <= 0) return false;
   if (d.pt < 0 || d.ph < 0 || d.pw < 0) return false;
@@ -896,72 +888,60 @@ static bool make_plan(const cstp_conv_desc& d, ConvPlan& p, bool with_affine = f
   p.Wo = (d.w + 2 * d.pw - d.kw) / d.sw + 1;
   if (p.Do <= 0 || p.Ho <= 0 || p.Wo <= 0) return false;
   p.ntaps = d.kt * d.kh * d.kw;
-  // forward: M = k, gather channels = c
-  if (!lookup_tuned(d, 0, p.f_t)) p.f_t = pick_tile(d.k, (long)d.n * p.Do * p.Ho * p.Wo, 1);
-  p.f_straddle = (d.c < 8);
-  // the split kernels address their operands with 31-bit buffer offsets (bit 31 = "masked")
-  const bool x_small = (size_t)d.n * d.c * d.d * d.h * d.w < (1ull << 29);
-  const bool y_small = (size_t)d.n * d.k * p.Do * p.Ho * p.Wo < (1ull << 29);
-  if (p.f_t.sp == 2 && !(x_small && y_small && patch_mt_ok(p.f_t.mt) && (patch_geom_ok(d) || tpatch_geom_ok(d)))) p.f_t = Tile{2, 1, 0, 1, 0};
-  // (the 3-channel stems run a split tile in its straddle mode: zero-padded input copy, per-k offset table, f16 pair only)
-  const bool stem_split_ok = p.f_straddle && p.f_t.sp == 1 && p.f_t.wm == 1 && (p.f_t.mt >= 4 && p.f_t.mt <= 6) &&
-                             split_planes() == 2 && p.ntaps * d.c <= STR_KMAX - 16 &&
-                             (size_t)d.n * d.c * (d.d + 2 * d.pt) * (d.h + 2 * d.ph) * (d.w + 2 * d.pw) < (1ull << 29);
-  if (p.f_t.sp == 1 && !stem_split_ok &&
-      (p.f_straddle || !x_small || p.ntaps > 27 || !split_tile_ok(p.f_t) || native_only()))
-    p.f_t = Tile{2, 1, 0, 1, 0};
-  if (p.f_t.sp == 1 && stem_split_ok && (!y_small || native_only())) p.f_t = Tile{2, 1, 0, 1, 0};
-  if (with_affine && x_small && y_small && k1w_preferred(d, p.f_t)) p.f_t = Tile{4, 2, 0, 1, 2};
-  p.f_Cp = p.f_straddle ? d.c : (int)align_up(d.c, 16);
+  p.straddle = (d.c < 8);
+  p.x_small = (size_t)d.n * d.c * d.d * d.h * d.w < (1ull << 29);
+  p.y_small = (size_t)d.n * d.k * p.Do * p.Ho * p.Wo < (1ull << 29);
+  p.f_Cp = p.straddle ? d.c : (int)align_up(d.c, 16);
   p.f_Kp = (int)align_up((size_t)p.ntaps * p.f_Cp, 16);
-  p.f_Mp = cdiv(d.k, tile_bm(p.f_t)) * tile_bm(p.f_t);
-  // dgrad: M = c, gather channels = k
-  if (!lookup_tuned(d, 1, p.d_t))
-    p.d_t = pick_tile(d.c, (long)d.n * cdiv(d.d, d.st) * cdiv(d.h, d.sh) * cdiv(d.w, d.sw), d.st * d.sh * d.sw);
-  if (p.d_t.sp == 2 && !(x_small && y_small && patch_mt_ok(p.d_t.mt) && (patch_geom_ok(d) || tpatch_geom_ok(d)))) p.d_t = Tile{2, 1, 0, 1, 0};
-  if (p.d_t.sp == 1 && (!y_small || p.ntaps > 27 || !split_tile_ok(p.d_t) || native_only())) p.d_t = Tile{2, 1, 0, 1, 0};
   p.d_Cp = (int)align_up(d.k, 16);
   p.d_Kp = p.ntaps * p.d_Cp;
-  p.d_Mp = cdiv(d.c, tile_bm(p.d_t)) * tile_bm(p.d_t);
-  // wgrad: M = k, J = (tap, c)
-  p.w_straddle = (d.c < 8);
-  p.w_mt = (CSTP_M16 && !p.w_straddle && d.k > 128 && d.k <= 144) ? 9 : pick_mt(d.k);   // 9 = nine 16-row tiles
-  p.w_blocks = 2048;   // ~8 blocks per CU: measured 12 % faster than 4 per CU over the R18 layer set
-  p.w_split = false;
-  p.w_patch = false;
-  p.w_tpatch = false;
-  {
-    Tile wt;
-    bool have_wt = lookup_tuned(d, 2, wt);
-    // developer override: CSTP_WTILE="s<mt>,<blocks/256>" forces the split weight-gradient kernel; unset in production
-    static const char* wov = getenv("CSTP_WTILE");
-    if (!have_wt && wov != nullptr && wov[0] == 'p') { wt = Tile{9, 1, 0, 0, 2}; have_wt = true; }
-    if (!have_wt && wov != nullptr && wov[0] == 's') {
-      int mt = 0, bl = 8;
-      if (sscanf(wov + 1, "%d,%d", &mt, &bl) >= 1 && (mt == 4 || mt == 8 || mt == 9)) { wt = Tile{mt, bl, 0, 0, 1}; have_wt = true; }
-    }
-    if (have_wt && wt.sp == 2) {       // igemm_k2p: x resident in LDS across the nine taps (144-row blocks, f16 pair)
-      p.w_patch = !p.w_straddle && x_small && y_small && wpatch_geom_ok(d);
-      p.w_tpatch = !p.w_straddle && x_small && y_small && twpatch_geom_ok(d);       // igemm_k2t: the temporal layers' stream kernel
-      have_wt = false;
-    }
-    if (have_wt) {
-      p.w_mt = wt.m16 ? 9 : wt.mt;
-      p.w_blocks = 256 * wt.wm;
-      // igemm_k2s (3xbf16 split): 128- or 144-row tiles, 31-bit buffer offsets
-      // (the 3-channel stems: igemm_k2s<.., STR> over the zero-padded input copy, f16 pair only)
-      const bool stem_ok = split_planes() == 2 && p.ntaps * d.c <= STR_KMAX - 16 &&
-                           (size_t)d.n * d.c * (d.d + 2 * d.pt) * (d.h + 2 * d.ph) * (d.w + 2 * d.pw) < (1ull << 29);
-      p.w_split = wt.sp && !native_only() && (!p.w_straddle || stem_ok) && x_small && y_small && (wt.mt == 4 || wt.mt == 8 || wt.mt == 9);
-      if (wt.sp && !p.w_split) p.w_mt = pick_mt(d.k);
-    }
-  }
-  p.w_Cp = p.w_straddle ? d.c : (int)align_up(d.c, 32);
+  p.w_Cp = p.straddle ? d.c : (int)align_up(d.c, 32);
   p.w_Jtot = p.ntaps * p.w_Cp;
   p.w_Jp = (int)align_up(p.w_Jtot, 32);
   return true;
 }
 
+// ---- one route per direction (route_forward / route_dgrad / route_wgrad below): which kernel serves THIS call, on which tile.
+// The facts of a call that the choice depends on, next to the descriptor:
+struct CallFacts {
+  bool bias = false;
+  int xform_groups = 0;      // > 0: the call carries an input transform (cstp_in_affine) over that many BatchNorm groups
+  bool cell = false;         // the caller gave the absmax cell of the gathered (forward, wgrad: transformed) activation
+  bool aligned = true;       // the activation tensors read and written start on 16-byte boundaries
+  int stats_groups = 0;      // forward: the next BatchNorm's partial sums are wanted, over that many groups
+  bool accumulate = false;
+  bool lin_aligned = false;  // the linear path (linear.h): activation, weights and workspace 16-byte aligned ...
+  size_t ws_bytes = 0;       // ... and the workspace that takes its partial sums (a query has none)
+};
+enum class Kern {
+  Linear,                    // linear.h
+  Native, NativeStraddle, NativeXform,      // igemm_k1 / igemm_k2 (f32 MFMA); straddle: the stems; xform: transform in the gather
+  Gather, GatherXform, GatherStem,          // igemm_k1s / igemm_k2s (igemm_split.h); stem: over the zero-padded input copy
+  Patch, TPatch, TWres       // igemm_k1p / igemm_k2p; igemm_k1t / igemm_k2t; igemm_k1w (forward only)
+};
+// t: the final tile (forward, dgrad: as in struct Tile; wgrad: mt row tiles, wm = split-K block target / 256, sp = 1 on igemm_k2s)
+// (Kern::Linear keeps the convolution kernels' tile: what cstp_conv3d_query_tile reports for these layers)
+struct Route {
+  Kern kern;
+  Tile t;
+  int Mp;                    // M padded to the tile height
+  bool fused;                // the input transform is applied inside the kernel
+  int nsplit;                // forward: partial sums per (channel, group) the kernel leaves; 0 = none
+};
+static const Tile NATIVE_2x1{2, 1, 0, 1, 0}, GATHER_144{9, 1, 0, 1, 1}, TWRES_64{4, 2, 0, 1, 2};
+static inline int pad_rows(int M, int bm) { return cdiv(M, bm) * bm; }
+
+// (the 3-channel stems run a split tile in its straddle mode: zero-padded input copy, per-k offset table, f16 pair only)
+static bool stem_fits(const cstp_conv_desc& d, const ConvPlan& p) {
+  return split_planes() == 2 && p.ntaps * d.c <= STR_KMAX - 16 &&
+         (size_t)d.n * d.c * (d.d + 2 * d.pt) * (d.h + 2 * d.ph) * (d.w + 2 * d.pw) < (1ull << 29);
+}
+
+// A FORWARD call that carries an input transform (cstp_in_affine: the BatchNorm + ReLU in front applied in the kernel's staging)
+// and no bias.  The tuner times plain forwards, where the gather kernel igemm_k1s wins the 64-row temporal layers of the
+// first stage (0.40 ms against 0.48 for igemm_k1w); WITH the transform the gather kernel pays it once per filter tap and cannot
+// leave the next BatchNorm's sums (0.524 ms + 0.075 ms of bn_reduce against 0.523 ms, sums included; same-box step A/B 56.57 ->
+// 55.97 ms, profiles/r04).  So such a call runs the weight-resident kernel wherever it applies (CSTP_K1W=0: the tuner's tile).
 static bool k1w_preferred(const cstp_conv_desc& d, const Tile& t) {
   static const bool on = [] { const char* e = getenv("CSTP_K1W"); return e == nullptr || atoi(e) != 0; }();
   if (!on || g_force_tile != nullptr) return false;                 // (a pinned / timed tile is run as given)
@@ -996,13 +976,15 @@ static bool linear_shape(const cstp_conv_desc& d) {
   return d.d == 1 && d.h == 1 && d.w == 1 && d.kt == 1 && d.kh == 1 && d.kw == 1 && d.st == 1 && d.sh == 1 && d.sw == 1 &&
          d.pt == 0 && d.ph == 0 && d.pw == 0 && d.n <= LIN_NMAX;
 }
-// returns false when the call does not qualify (alignment, workspace): the caller falls through to the convolution kernels
-static bool run_linear(hipStream_t s, const cstp_conv_desc& d, bool dgrad, const float* a, const float* w, const float* bias, float* out,
-                       void* ws, size_t ws_bytes, bool accumulate) {
+// ... and a forward / data-gradient call only with whole reduction slices, aligned operands and room for the partial sums; the
+// others run the convolution kernels
+static bool linear_served(const cstp_conv_desc& d, bool dgrad, const CallFacts& c) {
   const int R = dgrad ? d.k : d.c, J = dgrad ? d.c : d.k;            // reduction length, output features
-  if ((R % LIN_SLICE) != 0 || ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(w) | reinterpret_cast<uintptr_t>(ws)) & 15) != 0) return false;
-  const int S = R / LIN_SLICE;
-  if ((size_t)S * d.n * J * sizeof(float) > ws_bytes) return false;
+  return linear_shape(d) && (R % LIN_SLICE) == 0 && c.lin_aligned && (size_t)(R / LIN_SLICE) * d.n * J * sizeof(float) <= c.ws_bytes;
+}
+static void run_linear(hipStream_t s, const cstp_conv_desc& d, bool dgrad, const float* a, const float* w, const float* bias, float* out,
+                       void* ws, bool accumulate) {
+  const int J = dgrad ? d.c : d.k, S = (dgrad ? d.k : d.c) / LIN_SLICE;
   float* part = reinterpret_cast<float*>(ws);
   pack_clobbered(ws);
   const dim3 grid((unsigned)cdiv(J, 256), (unsigned)S);
@@ -1014,7 +996,6 @@ static bool run_linear(hipStream_t s, const cstp_conv_desc& d, bool dgrad, const
     else hipLaunchKernelGGL((linear_fwd_part_kernel<32>), grid, dim3(256), 0, s, a, w, part, d.n, d.c, d.k);
   }
   hipLaunchKernelGGL(linear_reduce_kernel, dim3((unsigned)cdiv(d.n * J, 256)), dim3(256), 0, s, part, bias, out, S, d.n, J, accumulate ? 1 : 0);
-  return true;
 }
 
 // deterministic mode (cstp_set_deterministic / CSTP_DETERMINISTIC=1): weight gradients through a two-stage split-K reduction
@@ -1033,6 +1014,11 @@ static bool deterministic() {
 // tail of the workspace: [0, 256) absmax cells of the activation operand(s), then the per-row inverse scales of the packed
 // weights (<= max(k, c) + 160 rows)
 static size_t plan_tail_bytes(const cstp_conv_desc& d) { return 256 + align_up((size_t)((d.k > d.c ? d.k : d.c) + 160) * 4, 256); }
+struct WsTail { unsigned* cells; float* inv_a; };
+static WsTail ws_tail(void* ws, size_t main_bytes) {
+  char* t = reinterpret_cast<char*>(ws) + main_bytes;
+  return WsTail{reinterpret_cast<unsigned*>(t), reinterpret_cast<float*>(t + 256)};
+}
 static size_t plan_main_bytes(const cstp_conv_desc& d, const ConvPlan& p);
 static size_t plan_ws_bytes(const cstp_conv_desc& d, const ConvPlan& p) { return plan_main_bytes(d, p) + plan_tail_bytes(d); }
 static size_t plan_main_bytes(const cstp_conv_desc& d, const ConvPlan& p) {
@@ -1272,7 +1258,44 @@ static int absmax_grid(size_t n) {
   return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b));
 }
 
+// the absmax cell of an activation operand of the f16-pair kernels: the caller's, else `cell`, filled here.
+// replayed_ws != nullptr (the forward / data-gradient side, whose pack kernel zeroes the cells): when the caller replayed the packs
+// -- possibly once for several calls on this workspace -- the cell is zeroed here, so that it holds THIS call's operand maximum
+// exactly.  (The weight gradient zeroes its cells together with the slab.)
+static const unsigned* operand_cell(hipStream_t s, const uint32_t* given, const float* src, size_t n, unsigned* cell,
+                                    const void* replayed_ws) {
+  if (given != nullptr) return given;
+  if (replayed_ws != nullptr && pack_skip(replayed_ws)) (void)hipMemsetAsync(cell, 0, 8, s);
+  hipLaunchKernelGGL(absmax_kernel, dim3(absmax_grid(n)), dim3(256), 0, s, src, n, cell);
+  return cell;
+}
+
+// the gather geometry: forward and weight gradient gather x over the positions of y, the data gradient gathers dy over the FULL
+// extents of x (its stride classes subsample inside)
+static Geom conv_geom(const cstp_conv_desc& d, const ConvPlan& p, bool dgrad, int Cp, int Mp, int Ktot) {
+  Geom g;
+  if (dgrad) { g.Cs = d.k; g.Ds = p.Do; g.Hs = p.Ho; g.Ws = p.Wo; g.Dp = d.d; g.Hp = d.h; g.Wp = d.w; g.M = d.c; }
+  else { g.Cs = d.c; g.Ds = d.d; g.Hs = d.h; g.Ws = d.w; g.Dp = p.Do; g.Hp = p.Ho; g.Wp = p.Wo; g.M = d.k; }
+  g.Nb = d.n;
+  g.kt = d.kt; g.kh = d.kh; g.kw = d.kw; g.st = d.st; g.sh = d.sh; g.sw = d.sw; g.pt = d.pt; g.ph = d.ph; g.pw = d.pw;
+  g.Cp = Cp; g.Mp = Mp; g.Ktot = Ktot;
+  return g;
+}
+// the stems on the f16-pair split kernels gather from a zero-padded copy of x, columns in (tap, c) order; the pad kernel leaves
+// the copy's absmax in cell[0] as a by-product
+static Geom stem_geom(Geom g, const cstp_conv_desc& d) {
+  g.Ds = d.d + 2 * d.pt; g.Hs = d.h + 2 * d.ph; g.Ws = d.w + 2 * d.pw;
+  g.pt = 0; g.ph = 0; g.pw = 0; g.Cp = d.c;
+  return g;
+}
+static void pad_stem_input(hipStream_t s, const cstp_conv_desc& d, const float* x, float* xp, unsigned* cell) {
+  const int nrows = d.n * d.c * (d.d + 2 * d.pt) * (d.h + 2 * d.ph);
+  const int pgrid = nrows / 4 < 2048 ? (nrows + 3) / 4 : 2048;
+  hipLaunchKernelGGL(pad_input_kernel, dim3(pgrid), dim3(256), 0, s, x, xp, cell, d.n * d.c, d.d, d.h, d.w, d.pt, d.ph, d.pw);
+}
+
 // pack the weights for the split kernel, make sure the gathered tensor's absmax cell is filled (NP == 2), launch it
+// (ia: Kern::GatherXform -- the gathered tensor is act(src * scale + shift) and src_absmax ITS maximum)
 template <bool DGRAD>
 static void run_k1s(const Tile& tl, dim3 grid, hipStream_t s, const Geom& g, const cstp_conv_desc& d, int ntaps, int Kp,
                     const float* w, const float* src, size_t src_elems, const float* bias, float* out, int ntx, int ntm,
@@ -1285,64 +1308,74 @@ static void run_k1s(const Tile& tl, dim3 grid, hipStream_t s, const Geom& g, con
     launch_k1s_np<DGRAD, 3>(tl, grid, s, g, reinterpret_cast<const uint4*>(ws), src, bias, out, ntx, ntm, nullptr, nullptr);
     return;
   }
-  unsigned* cells = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + main_bytes);
-  float* inv_a = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + main_bytes + 256);
-  pack_site_split2(s, w, reinterpret_cast<unsigned*>(ws), inv_a, cells, 1, d.k, d.c, ntaps, g.Cp, g.Mp, Kp / 16, DGRAD ? 1 : 0);
+  const WsTail t = ws_tail(ws, main_bytes);
+  pack_site_split2(s, w, reinterpret_cast<unsigned*>(ws), t.inv_a, t.cells, 1, d.k, d.c, ntaps, g.Cp, g.Mp, Kp / 16, DGRAD ? 1 : 0);
   if constexpr (!DGRAD) {
-    if (ia != nullptr && ia->ss != nullptr) {         // the gathered tensor is act(src * scale + shift); src_absmax is ITS maximum (checked by the caller)
-      launch_k1s_np<false, 2, true>(tl, grid, s, g, reinterpret_cast<const uint4*>(ws), src, bias, out, ntx, ntm, inv_a, src_absmax, ia);
+    if (ia != nullptr) {
+      launch_k1s_np<false, 2, true>(tl, grid, s, g, reinterpret_cast<const uint4*>(ws), src, bias, out, ntx, ntm, t.inv_a, src_absmax, ia);
       return;
     }
   }
-  if (src_absmax == nullptr) {
-    // (the pack kernel zeroes the cells; when the caller replayed the packs -- possibly once for several calls on this
-    //  workspace -- the cell is zeroed here, so that it holds THIS call's operand maximum exactly)
-    if (pack_skip(ws)) (void)hipMemsetAsync(cells, 0, 8, s);
-    hipLaunchKernelGGL(absmax_kernel, dim3(absmax_grid(src_elems)), dim3(256), 0, s, src, src_elems, cells);
-  }
-  launch_k1s_np<DGRAD, 2>(tl, grid, s, g, reinterpret_cast<const uint4*>(ws), src, bias, out, ntx, ntm, inv_a,
-                          src_absmax != nullptr ? src_absmax : cells);
+  const unsigned* bcell = operand_cell(s, src_absmax, src, src_elems, t.cells, ws);
+  launch_k1s_np<DGRAD, 2>(tl, grid, s, g, reinterpret_cast<const uint4*>(ws), src, bias, out, ntx, ntm, t.inv_a, bcell);
 }
 
 // the 3-channel stems on the f16-pair split kernel (igemm_k1s<.., STR = true>): zero-padded input copy (+ its absmax as a
 // by-product), weights packed in k = tap * c_in + c order, per-k offset table inside the kernel
-static void run_k1s_stem(const Tile& tl, hipStream_t s, const cstp_conv_desc& d, const ConvPlan& p, const float* w, const float* x,
+static void run_k1s_stem(const Route& r, hipStream_t s, const cstp_conv_desc& d, const ConvPlan& p, const float* w, const float* x,
                          const float* bias, float* y, void* ws, size_t main_bytes) {
-  const int Dq = d.d + 2 * d.pt, Hq = d.h + 2 * d.ph, Wq = d.w + 2 * d.pw;
-  const int kreal = p.ntaps * d.c, Kp = (int)align_up(kreal, 16);
-  const int bm = 16 * tl.mt, Mp = cdiv(d.k, bm) * bm;
-  const size_t packed = align_up((size_t)Kp * ((size_t)d.k + 160) * 6, 256);
+  const size_t packed = align_up((size_t)p.f_Kp * ((size_t)d.k + 160) * 6, 256);
   float* xp = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + packed);
-  unsigned* cells = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + main_bytes);
-  float* inv_a = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + main_bytes + 256);
-  pack_site_split2(s, w, reinterpret_cast<unsigned*>(ws), inv_a, cells, 1, d.k, d.c, p.ntaps, d.c, Mp, Kp / 16, 0);
-  {
-    const int nrows = d.n * d.c * Dq * Hq;
-    const int pgrid = nrows / 4 < 2048 ? (nrows + 3) / 4 : 2048;
-    if (pack_skip(ws)) (void)hipMemsetAsync(cells, 0, 8, s);       // (as above: the pad kernel takes the maximum into the cell)
-    hipLaunchKernelGGL(pad_input_kernel, dim3(pgrid), dim3(256), 0, s, x, xp, cells, d.n * d.c, d.d, d.h, d.w, d.pt, d.ph, d.pw);
-  }
-  Geom g;
-  g.Cs = d.c; g.Ds = Dq; g.Hs = Hq; g.Ws = Wq;
-  g.Nb = d.n; g.Dp = p.Do; g.Hp = p.Ho; g.Wp = p.Wo;
-  g.kt = d.kt; g.kh = d.kh; g.kw = d.kw; g.st = d.st; g.sh = d.sh; g.sw = d.sw; g.pt = 0; g.ph = 0; g.pw = 0;
-  g.Cp = d.c; g.M = d.k; g.Mp = Mp; g.Ktot = Kp;
+  const WsTail t = ws_tail(ws, main_bytes);
+  pack_site_split2(s, w, reinterpret_cast<unsigned*>(ws), t.inv_a, t.cells, 1, d.k, d.c, p.ntaps, d.c, r.Mp, p.f_Kp / 16, 0);
+  if (pack_skip(ws)) (void)hipMemsetAsync(t.cells, 0, 8, s);       // (as in operand_cell: the pad kernel takes the maximum into the cell)
+  pad_stem_input(s, d, x, xp, t.cells);
+  const Geom g = stem_geom(conv_geom(d, p, false, d.c, r.Mp, p.f_Kp), d);
   const int npos = d.n * p.Do * p.Ho * p.Wo;
-  const int ntx = cdiv(npos, 128), ntm = cdiv(d.k, bm);
+  const int ntx = cdiv(npos, 128), ntm = r.Mp / tile_bm(r.t);
   dim3 grid((unsigned)(align_up(ntx, 8) * ntm), 1, 1);
 #define CSTP_K1S_STR(MT_) \
   hipLaunchKernelGGL((igemm_k1s<MT_, false, 1, 2, true>), grid, dim3(512), 0, s, g, reinterpret_cast<const uint4*>(ws), xp, bias, \
-                     y, ntx, ntm, inv_a, cells, (const float2*)nullptr, 1, 0)
-  if (tl.mt == 4) CSTP_K1S_STR(4); else if (tl.mt == 5) CSTP_K1S_STR(5); else CSTP_K1S_STR(6);
+                     y, ntx, ntm, t.inv_a, t.cells, (const float2*)nullptr, 1, 0)
+  if (r.t.mt == 4) CSTP_K1S_STR(4); else if (r.t.mt == 5) CSTP_K1S_STR(5); else CSTP_K1S_STR(6);
 #undef CSTP_K1S_STR
 }
 
-// pack the weights for the patch kernel, make sure the gathered tensor's absmax cell is filled, launch it
-// (forward: src = x, Cs = c, M = k;  data gradient: src = dy, Cs = k, M = c -- a 3x3 stride-1 convolution with mirrored taps)
 // BatchNorm partial sums as a by-product of a forward patch launch (igemm_k1p<MT, true>): possible when every 224-position tile
 // is full and lies inside one BN group, the output allows 16-byte stores, and a block meets one row block only
 struct K1pStats { double* part; int groups; const float* pivot; unsigned* zcell; };
-static int k1p_grid_slots(const cstp_conv_desc& d, int M, int mt, int* ntiles_out, int* nmblk_out, int groups = 1);
+
+static int cu_count() {
+  static const int n_cu = [] {
+    int dev = 0, n = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+    // developer knob: CSTP_PERSIST_CUS=<n> caps the persistent kernels' grids (leaves CUs to kernels of the other stream)
+    const char* e = getenv("CSTP_PERSIST_CUS");
+    if (e != nullptr && atoi(e) >= 8 && atoi(e) < n) n = atoi(e);
+    return n > 8 ? n / 8 * 8 : 8;
+  }();
+  return n_cu;
+}
+
+// persistent blocks, one per CU (the LDS image fills it): 256 of them, or fewer when there is less work; returns slots per XCD
+// (groups > 1: a BatchNorm-statistics launch over that many view groups -- the slots of an XCD are dealt to the groups in turn,
+//  so their number is a multiple of groups * row blocks; 0 = no such grid)
+static int k1p_grid_slots(const cstp_conv_desc& d, int M, int mt, int* ntiles_out, int* nmblk_out, int groups = 1) {
+  const int n_cu = cu_count();
+  const long P = (long)d.n * d.d * d.h * d.w;
+  const int ntiles = (int)((P + KP_NPOS - 1) / KP_NPOS), nmblk = cdiv(M, 16 * mt);
+  if (ntiles_out) *ntiles_out = ntiles;
+  if (nmblk_out) *nmblk_out = nmblk;
+  if (groups > 1) {
+    const int per_xcd_g = cdiv(cdiv(ntiles, groups), 8) * nmblk * groups;
+    const int slots_g = per_xcd_g < n_cu / 8 ? per_xcd_g : n_cu / 8;
+    return slots_g / (groups * nmblk) * (groups * nmblk);
+  }
+  const int per_xcd = cdiv(ntiles, 8) * nmblk;        // items of the busiest XCD
+  const int slots = per_xcd < n_cu / 8 ? per_xcd : n_cu / 8;
+  return slots > 0 ? slots : 1;
+}
+
 static int k1p_stats_nsplit(const Tile& tl, const cstp_conv_desc& d, int groups) {
   if (tl.sp != 2 || groups < 1 || groups > 2 || d.n % groups != 0) return 0;
   const long gpos = (long)(d.n / groups) * d.d * d.h * d.w;
@@ -1354,8 +1387,24 @@ static int k1p_stats_nsplit(const Tile& tl, const cstp_conv_desc& d, int groups)
   return 8 * (slots / groups) / nmblk;
 }
 
-// the temporal layers: igemm_k1t (same packed-weight format with three taps, same grid, same partial-sum table)
-static void run_k1t(const Tile& tl, hipStream_t s, const cstp_conv_desc& d, bool dgrad, const float* w, const float* src,
+// what the two forward / data-gradient patch kernels share: the packed weights (nt taps), the gathered tensor's absmax cell, the
+// persistent grid
+struct K1pLaunch { WsTail t; const unsigned* bcell; int nmblk, ntiles; dim3 grid; double* part; const float* pivot; unsigned* zcell; };
+static K1pLaunch k1p_prepare(const Tile& tl, hipStream_t s, const cstp_conv_desc& d, bool dgrad, int nt, const float* w, const float* src,
+                             void* ws, size_t main_bytes, const uint32_t* src_absmax, const K1pStats* st) {
+  K1pLaunch L;
+  const int Cs = dgrad ? d.k : d.c, M = dgrad ? d.c : d.k, bm = 16 * tl.mt;
+  L.t = ws_tail(ws, main_bytes);
+  pack_site_patch(s, w, reinterpret_cast<uint4*>(ws), L.t.inv_a, L.t.cells, 1, d.k, d.c, cdiv(Cs, 32), bm, cdiv(M, bm) * bm, dgrad ? 1 : 0, nt);
+  L.bcell = operand_cell(s, src_absmax, src, (size_t)d.n * Cs * d.d * d.h * d.w, L.t.cells, ws);
+  L.grid = dim3((unsigned)(8 * k1p_grid_slots(d, M, tl.mt, &L.ntiles, &L.nmblk, st ? st->groups : 1)), 1, 1);
+  L.part = st ? st->part : nullptr; L.pivot = st ? st->pivot : nullptr; L.zcell = st ? st->zcell : nullptr;
+  return L;
+}
+
+// the temporal layers: igemm_k1t (same packed-weight format with three taps, same grid, same partial-sum table), or
+// (wres: Kern::TWres) the 64-row forward layers whose packed weights fit LDS whole: igemm_k1w (igemm_twres.h), tile {4, wm = 2, sp = 2}
+static void run_k1t(const Tile& tl, bool wres, hipStream_t s, const cstp_conv_desc& d, bool dgrad, const float* w, const float* src,
                     float* out, void* ws, size_t main_bytes, const uint32_t* src_absmax, const K1pStats* st, bool accumulate,
                     const InAffine* ia) {
   TGeom g{};
@@ -1368,42 +1417,25 @@ static void run_k1t(const Tile& tl, hipStream_t s, const cstp_conv_desc& d, bool
   g.gclips = st ? d.n / st->groups : 1;
   g.acc = accumulate ? 1 : 0;
   g.aff_npg = ia ? ia->npg : 1; g.aff_groups = ia ? ia->groups : 1; g.aff_relu = ia ? ia->relu : 0;
-  const int bm = 16 * tl.mt, nmblk = cdiv(g.M, bm);
+  const K1pLaunch L = k1p_prepare(tl, s, d, dgrad, 3, w, src, ws, main_bytes, src_absmax, st);
   const int ntiles = d.n * g.ndt * g.nwt;
-  unsigned* cells = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + main_bytes);
-  float* inv_a = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + main_bytes + 256);
-  pack_site_patch(s, w, reinterpret_cast<uint4*>(ws), inv_a, cells, 1, d.k, d.c, g.ncb, bm, nmblk * bm, dgrad ? 1 : 0, 3);
-  const size_t src_elems = (size_t)d.n * g.Cs * d.d * d.h * d.w;
-  if (src_absmax == nullptr) {
-    // (the pack kernel zeroes the cells; when the caller replayed the packs -- possibly once for several calls on this
-    //  workspace -- the cell is zeroed here, so that it holds THIS call's operand maximum exactly)
-    if (pack_skip(ws)) (void)hipMemsetAsync(cells, 0, 8, s);
-    hipLaunchKernelGGL(absmax_kernel, dim3(absmax_grid(src_elems)), dim3(256), 0, s, src, src_elems, cells);
-  }
-  const unsigned* bcell = src_absmax != nullptr ? src_absmax : cells;
-  const int slots = k1p_grid_slots(d, g.M, tl.mt, nullptr, nullptr, st ? st->groups : 1);
-  dim3 grid((unsigned)(8 * slots), 1, 1);
-  double* part = st ? st->part : nullptr;
-  const float* pivot = st ? st->pivot : nullptr;
-  unsigned* zcell = st ? st->zcell : nullptr;
   const float2* ss = ia ? ia->ss : nullptr;
-  // the 64-row forward layers whose packed weights fit LDS whole: igemm_k1w (igemm_twres.h), tile {4, wm = 2, sp = 2}
-  if (tl.wm == 2 && tl.mt == 4 && !dgrad && !accumulate && k1w_fits(g.M, g.Cs) && (ss == nullptr || g.Cs <= KW_AFFC)) {
+  if (wres) {
 #define CSTP_K1W_(ST_, AF_) \
-  hipLaunchKernelGGL((igemm_k1w<ST_, AF_>), grid, dim3(512), 0, s, g, reinterpret_cast<const uint4*>(ws), src, out, inv_a, bcell, ntiles, part, pivot, zcell, ss)
-    if (part != nullptr && ss != nullptr) CSTP_K1W_(true, true);
-    else if (part != nullptr) CSTP_K1W_(true, false);
+  hipLaunchKernelGGL((igemm_k1w<ST_, AF_>), L.grid, dim3(512), 0, s, g, reinterpret_cast<const uint4*>(ws), src, out, L.t.inv_a, L.bcell, ntiles, L.part, L.pivot, L.zcell, ss)
+    if (L.part != nullptr && ss != nullptr) CSTP_K1W_(true, true);
+    else if (L.part != nullptr) CSTP_K1W_(true, false);
     else if (ss != nullptr) CSTP_K1W_(false, true);
     else CSTP_K1W_(false, false);
 #undef CSTP_K1W_
     return;
   }
 #define CSTP_K1T_(MT_, ST_, AF_) \
-  hipLaunchKernelGGL((igemm_k1t<MT_, ST_, AF_>), grid, dim3(512), 0, s, g, reinterpret_cast<const uint4*>(ws), src, out, inv_a, bcell, ntiles, nmblk, part, pivot, zcell, ss)
+  hipLaunchKernelGGL((igemm_k1t<MT_, ST_, AF_>), L.grid, dim3(512), 0, s, g, reinterpret_cast<const uint4*>(ws), src, out, L.t.inv_a, L.bcell, ntiles, L.nmblk, L.part, L.pivot, L.zcell, ss)
 #define CSTP_K1T(MT_) \
   do { \
-    if (part != nullptr && ss != nullptr) CSTP_K1T_(MT_, true, true); \
-    else if (part != nullptr) CSTP_K1T_(MT_, true, false); \
+    if (L.part != nullptr && ss != nullptr) CSTP_K1T_(MT_, true, true); \
+    else if (L.part != nullptr) CSTP_K1T_(MT_, true, false); \
     else if (ss != nullptr) CSTP_K1T_(MT_, false, true); \
     else CSTP_K1T_(MT_, false, false); \
   } while (0)
@@ -1412,10 +1444,10 @@ static void run_k1t(const Tile& tl, hipStream_t s, const cstp_conv_desc& d, bool
 #undef CSTP_K1T_
 }
 
+// pack the weights for the patch kernel, make sure the gathered tensor's absmax cell is filled, launch it
+// (forward: src = x, Cs = c, M = k;  data gradient: src = dy, Cs = k, M = c -- a 3x3 stride-1 convolution with mirrored taps)
 static void run_k1p(const Tile& tl, hipStream_t s, const cstp_conv_desc& d, bool dgrad, const float* w, const float* src,
-                    float* out, void* ws, size_t main_bytes, const uint32_t* src_absmax, const K1pStats* st = nullptr,
-                    bool accumulate = false, const InAffine* ia = nullptr) {
-  if (tpatch_geom_ok(d)) { run_k1t(tl, s, d, dgrad, w, src, out, ws, main_bytes, src_absmax, st, accumulate, ia); return; }
+                    float* out, void* ws, size_t main_bytes, const uint32_t* src_absmax, const K1pStats* st, bool accumulate) {
   PGeom g;
   g.acc = accumulate ? 1 : 0;
   g.gpos = st ? (int)((long)(d.n / st->groups) * d.d * d.h * d.w) : 1;
@@ -1432,75 +1464,29 @@ static void run_k1p(const Tile& tl, hipStream_t s, const cstp_conv_desc& d, bool
     g.quad = quad_on && (g.W & 3) == 0 && (g.Cs & 7) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 &&
              lines * (g.W / 4) * 2 <= 192 && g.rows_lds + 32 <= KP_ROWS ? 1 : 0;
   }
-  const int bm = 16 * tl.mt, nmblk = cdiv(g.M, bm);
-  const long P = (long)g.NF * g.H * g.W;
-  const int ntiles = (int)((P + KP_NPOS - 1) / KP_NPOS);
-  unsigned* cells = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + main_bytes);
-  float* inv_a = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + main_bytes + 256);
-  pack_site_patch(s, w, reinterpret_cast<uint4*>(ws), inv_a, cells, 1, d.k, d.c, g.ncb, bm, nmblk * bm, dgrad ? 1 : 0, 9);
-  const size_t src_elems = (size_t)d.n * g.Cs * d.d * d.h * d.w;
-  if (src_absmax == nullptr) {
-    // (the pack kernel zeroes the cells; when the caller replayed the packs -- possibly once for several calls on this
-    //  workspace -- the cell is zeroed here, so that it holds THIS call's operand maximum exactly)
-    if (pack_skip(ws)) (void)hipMemsetAsync(cells, 0, 8, s);
-    hipLaunchKernelGGL(absmax_kernel, dim3(absmax_grid(src_elems)), dim3(256), 0, s, src, src_elems, cells);
-  }
-  const unsigned* bcell = src_absmax != nullptr ? src_absmax : cells;
-  const int slots = k1p_grid_slots(d, g.M, tl.mt, nullptr, nullptr, st ? st->groups : 1);
-  dim3 grid((unsigned)(8 * slots), 1, 1);
-  double* part = st ? st->part : nullptr;
-  const float* pivot = st ? st->pivot : nullptr;
-  unsigned* zcell = st ? st->zcell : nullptr;
+  const K1pLaunch L = k1p_prepare(tl, s, d, dgrad, 9, w, src, ws, main_bytes, src_absmax, st);
 #define CSTP_K1P(MT_) \
   do { \
-    if (part != nullptr) hipLaunchKernelGGL((igemm_k1p<MT_, true>), grid, dim3(512), 0, s, g, reinterpret_cast<const uint4*>(ws), src, out, inv_a, bcell, ntiles, nmblk, part, pivot, zcell); \
-    else hipLaunchKernelGGL((igemm_k1p<MT_, false>), grid, dim3(512), 0, s, g, reinterpret_cast<const uint4*>(ws), src, out, inv_a, bcell, ntiles, nmblk, part, pivot, zcell); \
+    if (L.part != nullptr) hipLaunchKernelGGL((igemm_k1p<MT_, true>), L.grid, dim3(512), 0, s, g, reinterpret_cast<const uint4*>(ws), src, out, L.t.inv_a, L.bcell, L.ntiles, L.nmblk, L.part, L.pivot, L.zcell); \
+    else hipLaunchKernelGGL((igemm_k1p<MT_, false>), L.grid, dim3(512), 0, s, g, reinterpret_cast<const uint4*>(ws), src, out, L.t.inv_a, L.bcell, L.ntiles, L.nmblk, L.part, L.pivot, L.zcell); \
   } while (0)
   if (tl.mt == 4) CSTP_K1P(4); else if (tl.mt == 8) CSTP_K1P(8); else CSTP_K1P(9);
 #undef CSTP_K1P
 }
 
-// persistent blocks, one per CU (the LDS image fills it): 256 of them, or fewer when there is less work; returns slots per XCD
-// (groups > 1: a BatchNorm-statistics launch over that many view groups -- the slots of an XCD are dealt to the groups in turn,
-//  so their number is a multiple of groups * row blocks; 0 = no such grid)
-static int k1p_grid_slots(const cstp_conv_desc& d, int M, int mt, int* ntiles_out, int* nmblk_out, int groups) {
-  static const int n_cu = [] {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    // developer knob: CSTP_PERSIST_CUS=<n> caps the persistent kernels' grids (leaves CUs to kernels of the other stream)
-    const char* e = getenv("CSTP_PERSIST_CUS");
-    if (e != nullptr && atoi(e) >= 8 && atoi(e) < n) n = atoi(e);
-    return n > 8 ? n / 8 * 8 : 8;
-  }();
-  const long P = (long)d.n * d.d * d.h * d.w;
-  const int ntiles = (int)((P + KP_NPOS - 1) / KP_NPOS), nmblk = cdiv(M, 16 * mt);
-  if (ntiles_out) *ntiles_out = ntiles;
-  if (nmblk_out) *nmblk_out = nmblk;
-  if (groups > 1) {
-    const int per_xcd_g = cdiv(cdiv(ntiles, groups), 8) * nmblk * groups;
-    const int slots_g = per_xcd_g < n_cu / 8 ? per_xcd_g : n_cu / 8;
-    return slots_g / (groups * nmblk) * (groups * nmblk);
-  }
-  const int per_xcd = cdiv(ntiles, 8) * nmblk;        // items of the busiest XCD
-  const int slots = per_xcd < n_cu / 8 ? per_xcd : n_cu / 8;
-  return slots > 0 ? slots : 1;
-}
-
-static int cu_count() {
-  static const int n_cu = [] {
-    int dev = 0, n = 256;
-    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    const char* e = getenv("CSTP_PERSIST_CUS");
-    if (e != nullptr && atoi(e) >= 8 && atoi(e) < n) n = atoi(e);
-    return n > 8 ? n / 8 * 8 : 8;
-  }();
-  return n_cu;
+// frame-range (igemm_k2p) / item-range (igemm_k2t) splits of one (row block, channel block) pair: the CUs shared among the pairs
+static int k2_range_splits(int ncombo, int nwork, bool det) {
+  int ns = cu_count() / ncombo;
+  if (ns < 1) ns = 1;
+  if (ns > nwork) ns = nwork;
+  if (det && ns > DET_MAX_SPLITS) ns = DET_MAX_SPLITS;
+  return ns;
 }
 
 // weight gradient on the LDS-resident x ring (igemm_k2p): one block per (144-row block, 32-channel block, frame range);
-// fills the packed slab(s) like igemm_k2s (scaled sums; unpack_wgrad_kernel applies the inverse operand scales)
+// fills the packed slab(s) like igemm_k2s (scaled sums; unpack_wgrad_kernel applies the inverse operand scales); returns the slabs
 static int run_k2p(hipStream_t s, const cstp_conv_desc& d, const ConvPlan& p, const float* x, const float* dy, float* dwp,
-                   const unsigned* xcell, const unsigned* dycell, bool det, size_t det_stride, int* nslabs_out) {
+                   const unsigned* xcell, const unsigned* dycell, bool det, size_t det_stride) {
   WPGeom g;
   g.C = d.c; g.M = d.k;
   g.ncb = cdiv(d.c, 32); g.nmblk = cdiv(d.k, WP_BM);
@@ -1511,23 +1497,17 @@ static int run_k2p(hipStream_t s, const cstp_conv_desc& d, const ConvPlan& p, co
   g.mg_hp1 = (unsigned)((1ull << 32) / (unsigned)(d.h + 1) + 1);
   g.mg_d = (unsigned)((1ull << 32) / (unsigned)d.d + 1);
   const int ncombo = g.ncb * g.nmblk;
-  int ns = cu_count() / ncombo;
-  if (ns < 1) ns = 1;
-  if (ns > g.NF) ns = g.NF;
-  if (det && ns > DET_MAX_SPLITS) ns = DET_MAX_SPLITS;
-  g.fper = cdiv(g.NF, ns);
+  g.fper = cdiv(g.NF, k2_range_splits(ncombo, g.NF, det));
   g.nsplit = cdiv(g.NF, g.fper);
   dim3 grid((unsigned)align_up((size_t)ncombo * g.nsplit, 8), 1, 1);
   hipLaunchKernelGGL(igemm_k2p, grid, dim3(512), 0, s, g, dy, x, dwp, xcell, dycell, det ? det_stride : (size_t)0);
-  *nslabs_out = det ? g.nsplit : 1;
-  return 0;
+  return det ? g.nsplit : 1;
 }
 
 // weight gradient of the temporal layers on streams of 32-position chunks (igemm_k2t): one block per (144 x-channels, 64 dY
-// channels, item range); slab(s) as igemm_k2p
+// channels, item range); slab(s) as igemm_k2p (ia: the transform of x inside; xcell is then T(x)'s)
 static int run_k2t(hipStream_t s, const cstp_conv_desc& d, const ConvPlan& p, const float* x, const float* dy, float* dwp,
-                   const unsigned* xcell, const unsigned* dycell, bool det, size_t det_stride, int* nslabs_out,
-                   const float2* ss, int aff_npg, int aff_groups, int aff_relu) {
+                   const unsigned* xcell, const unsigned* dycell, bool det, size_t det_stride, const InAffine& ia) {
   WTGeom g;
   g.C = d.c; g.M = d.k;
   g.nrb = cdiv(d.c, WP_BM); g.ncb = cdiv(d.k, 64);
@@ -1538,21 +1518,24 @@ static int run_k2t(hipStream_t s, const cstp_conv_desc& d, const ConvPlan& p, co
   g.Jp = p.w_Jp; g.Cp = p.w_Cp;
   g.mg_fp1 = (unsigned)((1ull << 32) / (unsigned)(d.d + 1) + 1);
   g.mg_nchunk = (unsigned)((1ull << 32) / (unsigned)g.nchunk + 1);
-  g.aff_npg = aff_npg; g.aff_groups = aff_groups; g.aff_relu = aff_relu;
+  g.aff_npg = ia.npg; g.aff_groups = ia.groups; g.aff_relu = ia.relu;
   const int ncombo = g.nrb * g.ncb;
-  int ns = cu_count() / ncombo;
-  if (ns < 1) ns = 1;
-  if (ns > g.nitems) ns = g.nitems;
-  if (det && ns > DET_MAX_SPLITS) ns = DET_MAX_SPLITS;
-  g.iper = cdiv(g.nitems, ns);
+  g.iper = cdiv(g.nitems, k2_range_splits(ncombo, g.nitems, det));
   g.nsplit = cdiv(g.nitems, g.iper);
   dim3 grid((unsigned)align_up((size_t)ncombo * g.nsplit, 8), 1, 1);
-#define CSTP_K2T(AF_, CH_) hipLaunchKernelGGL((igemm_k2t<AF_, CH_>), grid, dim3(512), 0, s, g, dy, x, dwp, xcell, dycell, det ? det_stride : (size_t)0, ss)
-  if (chunk == 32) { if (ss != nullptr) CSTP_K2T(true, 32); else CSTP_K2T(false, 32); }
-  else { if (ss != nullptr) CSTP_K2T(true, 16); else CSTP_K2T(false, 16); }
+#define CSTP_K2T(AF_, CH_) hipLaunchKernelGGL((igemm_k2t<AF_, CH_>), grid, dim3(512), 0, s, g, dy, x, dwp, xcell, dycell, det ? det_stride : (size_t)0, ia.ss)
+  if (chunk == 32) { if (ia.ss != nullptr) CSTP_K2T(true, 32); else CSTP_K2T(false, 32); }
+  else { if (ia.ss != nullptr) CSTP_K2T(true, 16); else CSTP_K2T(false, 16); }
 #undef CSTP_K2T
-  *nslabs_out = det ? g.nsplit : 1;
-  return 0;
+  return det ? g.nsplit : 1;
+}
+
+// the slab(s) of a weight gradient back into dw's layout (xcell / dycell: the f16-pair kernels' operand scales, else nullptr)
+static void unpack_wgrad(hipStream_t s, const cstp_conv_desc& d, const ConvPlan& p, const float* dwp, float* dw, const unsigned* xcell,
+                         const unsigned* dycell, int nslabs, size_t det_stride, bool accumulate) {
+  const size_t tot = (size_t)d.k * d.c * p.ntaps;
+  hipLaunchKernelGGL(unpack_wgrad_kernel, dim3(pack_grid(tot)), dim3(256), 0, s, dwp, dw, d.k, d.c, p.ntaps, p.w_Cp, p.w_Jp, xcell,
+                     dycell, nslabs, det_stride, accumulate ? 1 : 0);
 }
 
 static int parse_in_affine(const cstp_in_affine* a, const cstp_conv_desc& d, InAffine& o) {
@@ -1565,32 +1548,213 @@ static int parse_in_affine(const cstp_in_affine* a, const cstp_conv_desc& d, InA
   return 0;
 }
 
+// ---- the routes -------------------------------------------------------------------------------------------------------
 // Can a split (f16-pair gather) kernel apply the transform itself?  It needs the largest magnitude of the TRANSFORMED tensor
 // (absmax: the caller's cell, cstp_bn_finalize_pre), whole 16-channel groups, and column / K tiles (cols positions) that never
 // straddle two BatchNorm groups.
-static bool aff_split_ok(const cstp_conv_desc& d, const InAffine& ia, const uint32_t* absmax, long out_positions_per_clip, int cols) {
-  if (ia.ss == nullptr || absmax == nullptr || split_planes() != 2) return false;
-  if ((d.c & 15) != 0 || ia.groups > 2) return false;
-  const long gpos = (long)ia.npg * out_positions_per_clip;
+static bool aff_split_ok(const cstp_conv_desc& d, const CallFacts& c, long out_positions_per_clip, int cols) {
+  if (c.xform_groups < 1 || !c.cell || split_planes() != 2) return false;
+  if ((d.c & 15) != 0 || c.xform_groups > 2) return false;
+  const long gpos = (long)(d.n / c.xform_groups) * out_positions_per_clip;
   return gpos % cols == 0 && gpos < (1l << 30);
 }
+// ... or the temporal patch kernels (igemm_k1t / igemm_k1w<.., AFF>): tables of both groups in LDS, the transform once per staged
+// element; no bias
+static bool aff_tpatch_ok(const cstp_conv_desc& d, const CallFacts& c) {
+  return c.xform_groups >= 1 && c.xform_groups <= 2 && c.cell && !c.bias && c.aligned && tpatch_geom_ok(d) && d.c <= KT_AFFC;
+}
+// a patch tile (sp = 2) needs its layer and the 31-bit offsets; a gather tile (sp = 1) an instantiated shape, <= 27 taps, the
+// gathered tensor within 31-bit offsets; where not, the native 64 x 128 tile
+static bool patch_tile_ok(const cstp_conv_desc& d, const ConvPlan& p, const Tile& t) {
+  return p.x_small && p.y_small && patch_mt_ok(t.mt) && (patch_geom_ok(d) || tpatch_geom_ok(d));
+}
+static bool gather_tile_ok(const ConvPlan& p, const Tile& t, bool src_small) {
+  return src_small && p.ntaps <= 27 && split_tile_ok(t) && !native_only();
+}
+static Kern patch_kern(const cstp_conv_desc& d) { return tpatch_geom_ok(d) ? Kern::TPatch : Kern::Patch; }
 
-// ... or the temporal patch kernel (igemm_k1t<.., AFF>): tables of both groups in LDS, the transform once per staged element
-static bool aff_tpatch_ok(const cstp_conv_desc& d, const Tile& t, const InAffine& ia, const uint32_t* absmax, const void* x, const void* y) {
-  if (ia.ss == nullptr || absmax == nullptr || t.sp != 2 || !tpatch_geom_ok(d)) return false;
-  if (ia.groups > 2 || d.c > KT_AFFC) return false;
-  return ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0;
+static Route route_forward(const cstp_conv_desc& d, const ConvPlan& p, const CallFacts& c) {
+  const bool xform = c.xform_groups > 0;
+  const long S = (long)p.Do * p.Ho * p.Wo;
+  Route r{};
+  Tile& t = r.t;
+  if (!lookup_tuned(d, 0, t)) t = pick_tile(d.k, (long)d.n * S, 1);
+  // the tile the table or the model names, where this layer and arithmetic have it
+  if (t.sp == 2 && !patch_tile_ok(d, p, t)) t = NATIVE_2x1;
+  const bool stem = p.straddle && t.sp == 1 && t.wm == 1 && t.mt >= 4 && t.mt <= 6 && stem_fits(d, p) && p.y_small;
+  if (t.sp == 1 && !stem && (p.straddle || !gather_tile_ok(p, t, p.x_small))) t = NATIVE_2x1;
+  if (t.sp == 1 && stem && native_only()) t = NATIVE_2x1;
+  if (xform && !c.bias && p.x_small && p.y_small && k1w_preferred(d, t)) t = TWRES_64;
+  // the facts of this call
+  if (xform) r.fused = t.sp == 2 ? aff_tpatch_ok(d, c) : (t.sp == 1 && !p.straddle && aff_split_ok(d, c, S, tile_bn(t)));
+  // (the temporal patch kernels store / load 16 bytes per lane: misaligned tensors take the gather kernel)
+  if (t.sp == 2 && !c.aligned && tpatch_geom_ok(d)) t = GATHER_144;
+  if (t.sp != 0 && xform && !r.fused) {
+    // no fused input transform on this layer's split kernel: such a call runs a native tile (and its operand padding)
+    t = pick_tile(d.k, (long)d.n * S, 1);
+    if (t.sp) t = NATIVE_2x1;
+  }
+  if (t.sp == 2 && c.bias) t = GATHER_144;            // (a bias rides only on the Linear layers: never a 3x3 geometry)
+  r.Mp = pad_rows(d.k, tile_bm(t));
+  if (t.sp == 2) {
+    r.kern = patch_kern(d);
+    // the 64-row forward layers whose packed weights fit LDS whole (igemm_twres.h): tile {4, wm = 2, sp = 2}
+    if (r.kern == Kern::TPatch && t.wm == 2 && t.mt == 4 && k1w_fits(d.k, d.c) && (!r.fused || d.c <= KW_AFFC)) r.kern = Kern::TWres;
+    // the sums: no misaligned tensors, and a transform only inside the kernel (k1p_stats_nsplit: the grid's own conditions)
+    if (c.stats_groups > 0 && c.aligned && (!xform || r.fused)) r.nsplit = k1p_stats_nsplit(t, d, c.stats_groups);
+  } else if (t.sp == 1) {
+    r.kern = p.straddle ? Kern::GatherStem : r.fused ? Kern::GatherXform : Kern::Gather;
+  } else {
+    r.kern = p.straddle ? Kern::NativeStraddle : xform ? Kern::NativeXform : Kern::Native;
+  }
+  if (!xform && linear_served(d, false, c)) r.kern = Kern::Linear;
+  return r;
+}
+
+static Route route_dgrad(const cstp_conv_desc& d, const ConvPlan& p, const CallFacts& c) {
+  Route r{};
+  Tile& t = r.t;
+  if (!lookup_tuned(d, 1, t))
+    t = pick_tile(d.c, (long)d.n * cdiv(d.d, d.st) * cdiv(d.h, d.sh) * cdiv(d.w, d.sw), d.st * d.sh * d.sw);
+  if (t.sp == 2 && !patch_tile_ok(d, p, t)) t = NATIVE_2x1;
+  if (t.sp == 1 && !gather_tile_ok(p, t, p.y_small)) t = NATIVE_2x1;
+  if (t.sp == 2 && !c.aligned && tpatch_geom_ok(d)) t = GATHER_144;       // (as in route_forward)
+  r.Mp = pad_rows(d.c, tile_bm(t));
+  r.kern = t.sp == 2 ? patch_kern(d) : t.sp == 1 ? Kern::Gather : Kern::Native;
+  if (linear_served(d, true, c)) r.kern = Kern::Linear;
+  return r;
+}
+
+static inline int wgrad_bm(const Tile& t) { return t.sp ? 16 * t.mt : (t.mt == 9 ? 144 : 32 * t.mt); }   // native 9 = nine 16-row tiles
+static Route route_wgrad(const cstp_conv_desc& d, const ConvPlan& p, const CallFacts& c) {
+  const bool xform = c.xform_groups > 0;
+  const int native_mt = (CSTP_M16 && !p.straddle && d.k > 128 && d.k <= 144) ? 9 : pick_mt(d.k);
+  Route r{};
+  Tile& t = r.t;
+  t = Tile{native_mt, 8, 0, 0, 0};   // 2048 blocks = ~8 per CU: measured 12 % faster than 4 per CU over the R18 layer set
+  Tile wt;
+  bool have_wt = lookup_tuned(d, 2, wt);
+  // developer override: CSTP_WTILE="s<mt>,<blocks/256>" forces the split weight-gradient kernel; unset in production
+  static const char* wov = getenv("CSTP_WTILE");
+  if (!have_wt && wov != nullptr && wov[0] == 'p') { wt = Tile{9, 1, 0, 0, 2}; have_wt = true; }
+  if (!have_wt && wov != nullptr && wov[0] == 's') {
+    int mt = 0, bl = 8;
+    if (sscanf(wov + 1, "%d,%d", &mt, &bl) >= 1 && (mt == 4 || mt == 8 || mt == 9)) { wt = Tile{mt, bl, 0, 0, 1}; have_wt = true; }
+  }
+  bool split = false;
+  if (have_wt && wt.sp == 2) {
+    // igemm_k2p: x resident in LDS across the nine taps (144-row blocks, f16 pair), no transform; igemm_k2t: the temporal layers'
+    // stream kernel, both operands staged once (a transform of x inside: its cell is then T(x)'s); else the native default
+    const bool ok = !p.straddle && p.x_small && p.y_small;
+    if (ok && !xform && wpatch_geom_ok(d)) r.kern = Kern::Patch;
+    else if (ok && twpatch_geom_ok(d) && (!xform || (c.xform_groups <= 2 && c.cell))) { r.kern = Kern::TPatch; r.fused = xform; }
+    else have_wt = false;
+    if (have_wt) { t = wt; r.Mp = pad_rows(d.k, WP_BM); return r; }
+  }
+  if (have_wt) {
+    t.mt = wt.m16 ? 9 : wt.mt;
+    t.wm = wt.wm;
+    // igemm_k2s (3xbf16 split): 128- or 144-row tiles, 31-bit buffer offsets
+    // (the 3-channel stems: igemm_k2s<.., STR> over the zero-padded input copy, f16 pair only)
+    split = wt.sp && !native_only() && (!p.straddle || stem_fits(d, p)) && p.x_small && p.y_small && (wt.mt == 4 || wt.mt == 8 || wt.mt == 9);
+    if (wt.sp && !split) t.mt = pick_mt(d.k);
+  }
+  if (split && xform) {
+    // the fused input transform: on the f16-pair gather kernel (igemm_k2s<.., AFF>) where aff_split_ok, else the native kernel
+    // with its analytic tile
+    r.fused = !p.straddle && aff_split_ok(d, c, (long)p.Do * p.Ho * p.Wo, 32);
+    if (!r.fused) { split = false; t.mt = native_mt; }
+  }
+  t.sp = split ? 1 : 0;
+  r.Mp = pad_rows(d.k, wgrad_bm(t));
+  if (split) r.kern = p.straddle ? Kern::GatherStem : r.fused ? Kern::GatherXform : Kern::Gather;
+  else r.kern = p.straddle ? Kern::NativeStraddle : xform ? Kern::NativeXform : Kern::Native;
+  if (!xform && linear_shape(d)) r.kern = Kern::Linear;
+  return r;
+}
+
+// The call a query entry point describes is a training step's: aligned tensors, the absmax cell given, no bias.  A transform
+// counts where the kernel applies it; elsewhere the caller applies it in a pass of its own and the forward is a plain one.
+static CallFacts query_facts(int xform_groups, int stats_groups) {
+  CallFacts c;
+  c.cell = true; c.xform_groups = xform_groups; c.stats_groups = stats_groups;
+  return c;
+}
+static Route query_forward(const cstp_conv_desc& d, const ConvPlan& p, int xform_groups, int stats_groups) {
+  const Route r = route_forward(d, p, query_facts(xform_groups, stats_groups));
+  return xform_groups > 0 && !r.fused ? route_forward(d, p, query_facts(0, stats_groups)) : r;
+}
+
+// what every convolution entry point checks first
+static int conv_begin(bool pointers_given, const cstp_conv_desc* desc, size_t ws_bytes, ConvPlan& p) {
+  CSTP_REQUIRE(pointers_given, "null argument");
+  CSTP_REQUIRE(make_plan(*desc, p), "invalid conv descriptor");
+  CSTP_REQUIRE(ws_bytes >= plan_ws_bytes(*desc, p), "workspace too small");
+  const cstp_conv_desc& d = *desc;
+  CSTP_REQUIRE((size_t)d.n * d.c * d.d * d.h * d.w < (1ull << 30) && (size_t)d.n * d.k * p.Do * p.Ho * p.Wo < (1ull << 30),
+               "tensor too large for 32-bit byte offsets (>= 4 GiB)");
+  return 0;
+}
+static bool aligned16(const void* a, const void* b, const void* c = nullptr) {
+  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
+}
+
+// forward, with (st: cstp_conv3d_forward_bnstats) or without the next BatchNorm's partial sums
+static int conv_forward(void* stream, const cstp_conv_desc* desc, const float* x, const float* w, const float* bias,
+                        const cstp_in_affine* in_affine, float* y, void* ws, size_t ws_bytes, const uint32_t* x_absmax,
+                        const K1pStats* st, size_t part_bytes, int32_t* nsplit_out) {
+  ConvPlan p;
+  if (conv_begin(desc && x && w && y && ws, desc, ws_bytes, p)) return 1;
+  const cstp_conv_desc& d = *desc;
+  hipStream_t s = as_stream(stream);
+  InAffine ia;
+  if (parse_in_affine(in_affine, d, ia)) return 1;
+  CallFacts c;
+  c.bias = bias != nullptr; c.xform_groups = ia.ss != nullptr ? ia.groups : 0; c.cell = x_absmax != nullptr;
+  c.aligned = aligned16(x, y); c.stats_groups = st ? st->groups : 0;
+  c.lin_aligned = aligned16(x, w, ws); c.ws_bytes = ws_bytes;
+  const Route r = route_forward(d, p, c);
+  // this layer's kernel cannot deliver the sums (or cannot apply the input transform next to them): plain forward
+  if (r.nsplit == 0) st = nullptr;
+  else CSTP_REQUIRE(part_bytes >= ((size_t)d.k * st->groups * r.nsplit * 3 + d.k) * sizeof(double), "partial-sum buffer too small");
+  const size_t main_bytes = plan_main_bytes(d, p);
+  const InAffine* fused = r.fused ? &ia : nullptr;
+  const int npos = d.n * p.Do * p.Ho * p.Wo;
+  const int ntx = cdiv(npos, tile_bn(r.t)), ntm = r.Mp / tile_bm(r.t);
+  const dim3 grid((unsigned)(align_up(ntx, 8) * ntm), 1, 1);                 // (the native and gather kernels')
+  float* wp = reinterpret_cast<float*>(ws);
+  switch (r.kern) {
+    case Kern::Linear: run_linear(s, d, false, x, w, bias, y, ws, false); break;
+    case Kern::Patch: run_k1p(r.t, s, d, false, w, x, y, ws, main_bytes, x_absmax, st, false); break;
+    case Kern::TPatch:
+    case Kern::TWres: run_k1t(r.t, r.kern == Kern::TWres, s, d, false, w, x, y, ws, main_bytes, x_absmax, st, false, fused); break;
+    case Kern::GatherStem: run_k1s_stem(r, s, d, p, w, x, bias, y, ws, main_bytes); break;
+    case Kern::Gather:
+    case Kern::GatherXform:
+      run_k1s<false>(r.t, grid, s, conv_geom(d, p, false, p.f_Cp, r.Mp, p.ntaps * p.f_Cp), d, p.ntaps, p.f_Kp, w, x,
+                     (size_t)d.n * d.c * d.d * d.h * d.w, bias, y, ntx, ntm, ws, main_bytes, x_absmax, fused);
+      break;
+    default: {
+      pack_site_native(s, w, wp, d.k, d.c, p.ntaps, p.f_Cp, r.Mp, p.f_Kp, 0);
+      const Geom g = conv_geom(d, p, false, p.f_Cp, r.Mp, p.ntaps * p.f_Cp);
+      if (r.kern == Kern::NativeStraddle) launch_k1<false, true, false>(r.t, grid, s, g, wp, x, bias, y, ntx, ntm, nullptr, 1, 0);
+      else if (r.kern == Kern::NativeXform) launch_k1<false, false, true>(r.t, grid, s, g, wp, x, bias, y, ntx, ntm, ia.ss, ia.npg, ia.relu);
+      else launch_k1<false, false, false>(r.t, grid, s, g, wp, x, bias, y, ntx, ntm, nullptr, 1, 0);
+    }
+  }
+  CSTP_LAUNCH_CHECK();
+  if (nsplit_out != nullptr) *nsplit_out = r.nsplit;
+  return 0;
 }
 
 }  // namespace cstp
 
 using namespace cstp;
 
+// (sized for the tallest row padding, so it is the same for every route of the layer: plan_main_bytes)
 extern "C" size_t cstp_conv3d_workspace_bytes(const cstp_conv_desc* desc) {
-  ConvPlan p, pa;
-  if (desc == nullptr || !make_plan(*desc, p) || !make_plan(*desc, pa, true)) return 0;
-  const size_t a = plan_ws_bytes(*desc, p), b = plan_ws_bytes(*desc, pa);      // (a forward with an input transform may run another tile)
-  return a > b ? a : b;
+  ConvPlan p;
+  return desc != nullptr && make_plan(*desc, p) ? plan_ws_bytes(*desc, p) : 0;
 }
 
 extern "C" int cstp_conv3d_forward(void* stream, const cstp_conv_desc* desc, const float* x, const float* w,
@@ -1601,125 +1765,37 @@ extern "C" int cstp_conv3d_forward(void* stream, const cstp_conv_desc* desc, con
 
 extern "C" int32_t cstp_conv3d_in_affine_fused(const cstp_conv_desc* desc, int32_t groups) {
   ConvPlan p;
-  if (desc == nullptr || !make_plan(*desc, p, true) || groups < 1 || desc->n % groups != 0) return 0;
-  const cstp_conv_desc& d = *desc;
-  InAffine ia{reinterpret_cast<const float2*>(desc), d.n / groups, groups, 1};       // (ss: any non-null pointer, never read here)
-  const uint32_t* some = reinterpret_cast<const uint32_t*>(desc);
-  const long S = (long)p.Do * p.Ho * p.Wo;
-  const bool fwd = (p.f_t.sp == 1 && !p.f_straddle && aff_split_ok(d, ia, some, S, tile_bn(p.f_t))) ||
-                   aff_tpatch_ok(d, p.f_t, ia, some, nullptr, nullptr);
-  const bool wgr = (p.w_split && !p.w_straddle && !p.w_patch && !p.w_tpatch && aff_split_ok(d, ia, some, S, 32)) ||
-                   (p.w_tpatch && groups <= 2);
-  return fwd && wgr ? 1 : 0;
+  if (desc == nullptr || !make_plan(*desc, p) || groups < 1 || desc->n % groups != 0) return 0;
+  const CallFacts c = query_facts(groups, 0);
+  return route_forward(*desc, p, c).fused && route_wgrad(*desc, p, c).fused ? 1 : 0;
 }
 
 extern "C" int32_t cstp_conv3d_bnstats_nsplit(const cstp_conv_desc* desc, int32_t groups) {
   ConvPlan p;
   if (desc == nullptr || !make_plan(*desc, p)) return 0;
-  return k1p_stats_nsplit(p.f_t, *desc, groups);
+  return query_forward(*desc, p, 0, groups).nsplit;
 }
 
 extern "C" int32_t cstp_conv3d_bnstats_nsplit_aff(const cstp_conv_desc* desc, int32_t groups) {
   ConvPlan p;
-  if (desc == nullptr || !make_plan(*desc, p, true)) return 0;
-  return k1p_stats_nsplit(p.f_t, *desc, groups);
+  if (desc == nullptr || !make_plan(*desc, p)) return 0;
+  return query_forward(*desc, p, groups, groups).nsplit;
 }
 
 extern "C" int cstp_conv3d_forward_bnstats(void* stream, const cstp_conv_desc* desc, const float* x, const float* w, float* y,
                                            void* ws, size_t ws_bytes, const uint32_t* x_absmax, int32_t groups, const float* pivot,
                                            double* part, size_t part_bytes, int32_t* nsplit_out, uint32_t* z_cell,
                                            const cstp_in_affine* in_affine) {
-  CSTP_REQUIRE(desc && x && w && y && ws && part && nsplit_out, "null argument");
-  ConvPlan p;
-  CSTP_REQUIRE(make_plan(*desc, p, in_affine != nullptr && in_affine->scale_shift != nullptr), "invalid conv descriptor");
-  InAffine ia;
-  if (parse_in_affine(in_affine, *desc, ia)) return 1;
-  const int ns = k1p_stats_nsplit(p.f_t, *desc, groups);
+  CSTP_REQUIRE(part && nsplit_out, "null argument");
   *nsplit_out = 0;
-  // this layer's kernel cannot deliver the sums (or cannot apply the input transform next to them): plain forward
-  if (ns == 0 || ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(x)) & 15) != 0 ||
-      (ia.ss != nullptr && !aff_tpatch_ok(*desc, p.f_t, ia, x_absmax, x, y)))
-    return cstp_conv3d_forward_am(stream, desc, x, w, nullptr, in_affine, y, ws, ws_bytes, x_absmax);
-  CSTP_REQUIRE(ws_bytes >= plan_ws_bytes(*desc, p), "workspace too small");
-  CSTP_REQUIRE(part_bytes >= ((size_t)desc->k * groups * ns * 3 + desc->k) * sizeof(double), "partial-sum buffer too small");
-  const cstp_conv_desc& d = *desc;
-  CSTP_REQUIRE((size_t)d.n * d.c * d.d * d.h * d.w < (1ull << 30) && (size_t)d.n * d.k * p.Do * p.Ho * p.Wo < (1ull << 30),
-               "tensor too large for 32-bit byte offsets (>= 4 GiB)");
   const K1pStats st{part, groups, pivot, z_cell};
-  run_k1p(p.f_t, as_stream(stream), d, false, w, x, y, ws, plan_main_bytes(d, p), x_absmax, &st, false, ia.ss != nullptr ? &ia : nullptr);
-  CSTP_LAUNCH_CHECK();
-  *nsplit_out = ns;
-  return 0;
+  return conv_forward(stream, desc, x, w, nullptr, in_affine, y, ws, ws_bytes, x_absmax, &st, part_bytes, nsplit_out);
 }
 
 extern "C" int cstp_conv3d_forward_am(void* stream, const cstp_conv_desc* desc, const float* x, const float* w,
                                       const float* bias, const cstp_in_affine* in_affine, float* y, void* ws,
                                       size_t ws_bytes, const uint32_t* x_absmax) {
-  CSTP_REQUIRE(desc && x && w && y && ws, "null argument");
-  ConvPlan p;
-  CSTP_REQUIRE(make_plan(*desc, p, bias == nullptr && in_affine != nullptr && in_affine->scale_shift != nullptr), "invalid conv descriptor");
-  CSTP_REQUIRE(ws_bytes >= plan_ws_bytes(*desc, p), "workspace too small");
-  const cstp_conv_desc& d = *desc;
-  CSTP_REQUIRE((size_t)d.n * d.c * d.d * d.h * d.w < (1ull << 30) && (size_t)d.n * d.k * p.Do * p.Ho * p.Wo < (1ull << 30),
-               "tensor too large for 32-bit byte offsets (>= 4 GiB)");
-  hipStream_t s = as_stream(stream);
-  float* wp = reinterpret_cast<float*>(ws);
-  InAffine ia;
-  if (parse_in_affine(in_affine, d, ia)) return 1;
-  if (ia.ss == nullptr && linear_shape(d) && run_linear(s, d, false, x, w, bias, y, ws, ws_bytes, false)) {
-    CSTP_LAUNCH_CHECK();
-    return 0;
-  }
-  // the fused input transform on the f16-pair gather kernel (igemm_k1s<.., AFF>): see aff_split_ok
-  const bool aff_split = ia.ss != nullptr && p.f_t.sp == 1 && !p.f_straddle &&
-                         aff_split_ok(d, ia, x_absmax, (long)p.Do * p.Ho * p.Wo, tile_bn(p.f_t));
-  const bool aff_tpatch = bias == nullptr && aff_tpatch_ok(d, p.f_t, ia, x_absmax, x, y);
-  // (the patch kernels store / load 16 bytes per lane: misaligned tensors take the gather kernel)
-  if (p.f_t.sp == 2 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) != 0 && tpatch_geom_ok(d)) {
-    p.f_t = Tile{9, 1, 0, 1, 1};
-    p.f_Mp = cdiv(d.k, tile_bm(p.f_t)) * tile_bm(p.f_t);
-  }
-  if (p.f_t.sp != 0 && ia.ss != nullptr && !aff_split && !aff_tpatch) {
-    // no fused input transform on this layer's split kernel: such a call runs a native tile (and its operand padding)
-    p.f_t = pick_tile(d.k, (long)d.n * p.Do * p.Ho * p.Wo, 1);
-    if (p.f_t.sp) p.f_t = Tile{2, 1, 0, 1, 0};
-    p.f_Mp = cdiv(d.k, tile_bm(p.f_t)) * tile_bm(p.f_t);
-  }
-  if (p.f_t.sp == 2 && bias == nullptr) {
-    run_k1p(p.f_t, s, d, false, w, x, y, ws, plan_main_bytes(d, p), x_absmax, nullptr, false, aff_tpatch ? &ia : nullptr);
-    CSTP_LAUNCH_CHECK();
-    return 0;
-  }
-  if (p.f_t.sp == 1 && p.f_straddle && !(in_affine != nullptr && in_affine->scale_shift != nullptr)) {
-    run_k1s_stem(p.f_t, s, d, p, w, x, bias, y, ws, plan_main_bytes(d, p));
-    CSTP_LAUNCH_CHECK();
-    return 0;
-  }
-  if (p.f_t.sp == 2) {                               // (a bias rides only on the Linear layers: never a 3x3 geometry)
-    p.f_t = Tile{9, 1, 0, 1, 1};
-    if (!split_tile_ok(p.f_t) || p.f_straddle) p.f_t = Tile{2, 1, 0, 1, 0};
-    p.f_Mp = cdiv(d.k, tile_bm(p.f_t)) * tile_bm(p.f_t);
-  }
-  const size_t tot = (size_t)p.f_Kp * p.f_Mp;
-  const bool f_split = p.f_t.sp && !p.f_straddle;
-  if (!f_split)
-    pack_site_native(s, w, wp, d.k, d.c, p.ntaps, p.f_Cp, p.f_Mp, p.f_Kp, 0);
-  Geom g;
-  g.Cs = d.c; g.Ds = d.d; g.Hs = d.h; g.Ws = d.w;
-  g.Nb = d.n; g.Dp = p.Do; g.Hp = p.Ho; g.Wp = p.Wo;
-  g.kt = d.kt; g.kh = d.kh; g.kw = d.kw; g.st = d.st; g.sh = d.sh; g.sw = d.sw; g.pt = d.pt; g.ph = d.ph; g.pw = d.pw;
-  g.Cp = p.f_Cp; g.M = d.k; g.Mp = p.f_Mp; g.Ktot = p.ntaps * p.f_Cp;
-  const int npos = d.n * p.Do * p.Ho * p.Wo;
-  const int f_bm = tile_bm(p.f_t), f_bn = tile_bn(p.f_t);
-  const int ntx = cdiv(npos, f_bn), ntm = cdiv(d.k, f_bm);
-  dim3 grid((unsigned)(align_up(ntx, 8) * ntm), 1, 1);
-  if (f_split) run_k1s<false>(p.f_t, grid, s, g, d, p.ntaps, p.f_Kp, w, x, (size_t)d.n * d.c * d.d * d.h * d.w, bias, y, ntx, ntm,
-                              ws, plan_main_bytes(d, p), x_absmax, aff_split ? &ia : nullptr);
-  else if (p.f_straddle) launch_k1<false, true, false>(p.f_t, grid, s, g, wp, x, bias, y, ntx, ntm, nullptr, 1, 0);
-  else if (ia.ss) launch_k1<false, false, true>(p.f_t, grid, s, g, wp, x, bias, y, ntx, ntm, ia.ss, ia.npg, ia.relu);
-  else launch_k1<false, false, false>(p.f_t, grid, s, g, wp, x, bias, y, ntx, ntm, nullptr, 1, 0);
-  CSTP_LAUNCH_CHECK();
-  return 0;
+  return conv_forward(stream, desc, x, w, bias, in_affine, y, ws, ws_bytes, x_absmax, nullptr, 0, nullptr);
 }
 
 extern "C" int cstp_conv3d_backward_data(void* stream, const cstp_conv_desc* desc, const float* dy, const float* w,
@@ -1735,51 +1811,39 @@ extern "C" int cstp_conv3d_backward_data_am(void* stream, const cstp_conv_desc* 
 extern "C" int cstp_conv3d_backward_data_acc(void* stream, const cstp_conv_desc* desc, const float* dy, const float* w,
                                              float* dx, void* ws, size_t ws_bytes, const uint32_t* dy_absmax,
                                              int32_t accumulate) {
-  CSTP_REQUIRE(desc && dy && w && dx && ws, "null argument");
   ConvPlan p;
-  CSTP_REQUIRE(make_plan(*desc, p), "invalid conv descriptor");
-  CSTP_REQUIRE(ws_bytes >= plan_ws_bytes(*desc, p), "workspace too small");
+  if (conv_begin(desc && dy && w && dx && ws, desc, ws_bytes, p)) return 1;
   const cstp_conv_desc& d = *desc;
-  CSTP_REQUIRE((size_t)d.n * d.c * d.d * d.h * d.w < (1ull << 30) && (size_t)d.n * d.k * p.Do * p.Ho * p.Wo < (1ull << 30),
-               "tensor too large for 32-bit byte offsets (>= 4 GiB)");
   hipStream_t s = as_stream(stream);
-  float* wp = reinterpret_cast<float*>(ws);
-  if (linear_shape(d) && run_linear(s, d, true, dy, w, nullptr, dx, ws, ws_bytes, accumulate != 0)) {
-    CSTP_LAUNCH_CHECK();
-    return 0;
+  CallFacts c;
+  c.cell = dy_absmax != nullptr; c.aligned = aligned16(dy, dx); c.accumulate = accumulate != 0;
+  c.lin_aligned = aligned16(dy, w, ws); c.ws_bytes = ws_bytes;
+  const Route r = route_dgrad(d, p, c);
+  const size_t main_bytes = plan_main_bytes(d, p);
+  switch (r.kern) {
+    case Kern::Linear: run_linear(s, d, true, dy, w, nullptr, dx, ws, c.accumulate); break;
+    case Kern::Patch: run_k1p(r.t, s, d, true, w, dy, dx, ws, main_bytes, dy_absmax, nullptr, c.accumulate); break;
+    case Kern::TPatch: run_k1t(r.t, false, s, d, true, w, dy, dx, ws, main_bytes, dy_absmax, nullptr, c.accumulate, nullptr); break;
+    default: {
+      float* wp = reinterpret_cast<float*>(ws);
+      if (r.kern == Kern::Native) pack_site_native(s, w, wp, d.k, d.c, p.ntaps, p.d_Cp, r.Mp, p.d_Kp, 1);
+      Geom g = conv_geom(d, p, true, p.d_Cp, r.Mp, p.ntaps * p.d_Cp);
+      g.acc = accumulate ? 1 : 0;
+      const int nclass = d.st * d.sh * d.sw;
+      const int npos_max = d.n * cdiv(d.d, d.st) * cdiv(d.h, d.sh) * cdiv(d.w, d.sw);
+      const int ntx = cdiv(npos_max, tile_bn(r.t)), ntm = r.Mp / tile_bm(r.t);
+      dim3 grid((unsigned)(align_up(ntx, 8) * ntm), (unsigned)nclass, 1);
+      if (p.ntaps == 1 && nclass > 1 && d.pt == 0 && d.ph == 0 && d.pw == 0) {
+        // a strided pointwise layer (the shortcut's spatial half, r21d_byol.py:122-125): only stride class 0 holds a tap, the other
+        // positions of dx are exact zeros -- one fill instead of three classes of strided zero stores (or nothing when accumulating)
+        if (!accumulate) CSTP_REQUIRE(hipMemsetAsync(dx, 0, (size_t)d.n * d.c * d.d * d.h * d.w * sizeof(float), s) == hipSuccess, "hipMemsetAsync");
+        grid.y = 1;
+      }
+      if (r.kern == Kern::Gather) run_k1s<true>(r.t, grid, s, g, d, p.ntaps, p.d_Kp, w, dy, (size_t)d.n * d.k * p.Do * p.Ho * p.Wo, nullptr, dx, ntx,
+                                                ntm, ws, main_bytes, dy_absmax);
+      else launch_k1<true, false, false>(r.t, grid, s, g, wp, dy, nullptr, dx, ntx, ntm, nullptr, 1, 0);
+    }
   }
-  if (p.d_t.sp == 2 && tpatch_geom_ok(d) && ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15) != 0) {
-    p.d_t = Tile{9, 1, 0, 1, 1};
-    p.d_Mp = cdiv(d.c, tile_bm(p.d_t)) * tile_bm(p.d_t);
-  }
-  if (p.d_t.sp == 2) {
-    run_k1p(p.d_t, s, d, true, w, dy, dx, ws, plan_main_bytes(d, p), dy_absmax, nullptr, accumulate != 0);
-    CSTP_LAUNCH_CHECK();
-    return 0;
-  }
-  const size_t tot = (size_t)p.d_Kp * p.d_Mp;
-  const bool d_split = p.d_t.sp != 0;
-  if (!d_split) pack_site_native(s, w, wp, d.k, d.c, p.ntaps, p.d_Cp, p.d_Mp, p.d_Kp, 1);
-  Geom g;
-  g.Cs = d.k; g.Ds = p.Do; g.Hs = p.Ho; g.Ws = p.Wo;     // gather from dy
-  g.Nb = d.n; g.Dp = d.d; g.Hp = d.h; g.Wp = d.w;         // FULL x dims; classes subsample inside
-  g.kt = d.kt; g.kh = d.kh; g.kw = d.kw; g.st = d.st; g.sh = d.sh; g.sw = d.sw; g.pt = d.pt; g.ph = d.ph; g.pw = d.pw;
-  g.Cp = p.d_Cp; g.M = d.c; g.Mp = p.d_Mp; g.Ktot = p.ntaps * p.d_Cp;
-  g.acc = accumulate ? 1 : 0;
-  const int nclass = d.st * d.sh * d.sw;
-  const int npos_max = d.n * cdiv(d.d, d.st) * cdiv(d.h, d.sh) * cdiv(d.w, d.sw);
-  const int d_bm = tile_bm(p.d_t), d_bn = tile_bn(p.d_t);
-  const int ntx = cdiv(npos_max, d_bn), ntm = cdiv(d.c, d_bm);
-  dim3 grid((unsigned)(align_up(ntx, 8) * ntm), (unsigned)nclass, 1);
-  if (p.ntaps == 1 && nclass > 1 && d.pt == 0 && d.ph == 0 && d.pw == 0) {
-    // a strided pointwise layer (the shortcut's spatial half, r21d_byol.py:122-125): only stride class 0 holds a tap, the other
-    // positions of dx are exact zeros -- one fill instead of three classes of strided zero stores (or nothing when accumulating)
-    if (!accumulate) CSTP_REQUIRE(hipMemsetAsync(dx, 0, (size_t)d.n * d.c * d.d * d.h * d.w * sizeof(float), s) == hipSuccess, "hipMemsetAsync");
-    grid.y = 1;
-  }
-  if (d_split) run_k1s<true>(p.d_t, grid, s, g, d, p.ntaps, p.d_Kp, w, dy, (size_t)d.n * d.k * p.Do * p.Ho * p.Wo, nullptr, dx, ntx,
-                             ntm, ws, plan_main_bytes(d, p), dy_absmax);
-  else launch_k1<true, false, false>(p.d_t, grid, s, g, wp, dy, nullptr, dx, ntx, ntm, nullptr, 1, 0);
   CSTP_LAUNCH_CHECK();
   return 0;
 }
@@ -1852,157 +1916,113 @@ extern "C" int cstp_conv3d_backward_weight_acc(void* stream, const cstp_conv_des
                                                const cstp_in_affine* in_affine, const float* dy, float* dw, void* ws,
                                                size_t ws_bytes, const uint32_t* x_absmax, const uint32_t* dy_absmax,
                                                int32_t accumulate) {
-  CSTP_REQUIRE(desc && x && dy && dw && ws, "null argument");
   ConvPlan p;
-  CSTP_REQUIRE(make_plan(*desc, p), "invalid conv descriptor");
-  CSTP_REQUIRE(ws_bytes >= plan_ws_bytes(*desc, p), "workspace too small");
+  if (conv_begin(desc && x && dy && dw && ws, desc, ws_bytes, p)) return 1;
   const cstp_conv_desc& d = *desc;
-  CSTP_REQUIRE((size_t)d.n * d.c * d.d * d.h * d.w < (1ull << 30) && (size_t)d.n * d.k * p.Do * p.Ho * p.Wo < (1ull << 30),
-               "tensor too large for 32-bit byte offsets (>= 4 GiB)");
   hipStream_t s = as_stream(stream);
-  float* dwp = reinterpret_cast<float*>(ws);
-  const size_t slab = (size_t)d.k * p.w_Jp * sizeof(float);
-  // the absmax cells of the 2xf16-split kernel sit right behind the slab (256-byte aligned) and are zeroed with it
-  const size_t slab_al = align_up(slab, 256);
-  const bool det = deterministic();
-  Geom g;
-  g.Cs = d.c; g.Ds = d.d; g.Hs = d.h; g.Ws = d.w;         // gather from x
-  g.Nb = d.n; g.Dp = p.Do; g.Hp = p.Ho; g.Wp = p.Wo;      // reduction over dy positions
-  g.kt = d.kt; g.kh = d.kh; g.kw = d.kw; g.st = d.st; g.sh = d.sh; g.sw = d.sw; g.pt = d.pt; g.ph = d.ph; g.pw = d.pw;
-  g.Cp = p.w_Cp; g.M = d.k; g.Mp = 0; g.Ktot = p.w_Jtot;
   InAffine ia;
   if (parse_in_affine(in_affine, d, ia)) return 1;
-  if (ia.ss == nullptr && linear_shape(d)) {
+  CallFacts c;
+  c.xform_groups = ia.ss != nullptr ? ia.groups : 0; c.cell = x_absmax != nullptr; c.accumulate = accumulate != 0;
+  const Route r = route_wgrad(d, p, c);
+  if (r.kern == Kern::Linear) {
     const dim3 lgrid((unsigned)cdiv(d.c, 256), (unsigned)cdiv(d.k, 16));
     if (d.n <= 16) hipLaunchKernelGGL((linear_wgrad_kernel<16>), lgrid, dim3(256), 0, s, dy, x, dw, d.n, d.c, d.k, accumulate ? 1 : 0);
     else hipLaunchKernelGGL((linear_wgrad_kernel<32>), lgrid, dim3(256), 0, s, dy, x, dw, d.n, d.c, d.k, accumulate ? 1 : 0);
     CSTP_LAUNCH_CHECK();
     return 0;
   }
-  if (p.w_patch && ia.ss == nullptr) {
-    // igemm_k2p.  Slab(s) + absmax cells zeroed together; in deterministic mode one slab per frame-range split.
-    const size_t det_stride_p = det ? slab_al / sizeof(float) : 0;
-    int ns_max = cu_count() / (cdiv(d.c, 32) * cdiv(d.k, WP_BM));
+  float* dwp = reinterpret_cast<float*>(ws);
+  // one slab filled by atomics, or (deterministic) one slab per split; the absmax cells of the f16-pair kernels sit right behind
+  // the slab(s), 256-byte aligned, and are zeroed with them
+  const size_t slab_al = align_up((size_t)d.k * p.w_Jp * sizeof(float), 256);
+  const bool det = deterministic();
+  const size_t det_stride = det ? slab_al / sizeof(float) : 0;
+  const size_t nx = (size_t)d.n * d.c * d.d * d.h * d.w, ny = (size_t)d.n * d.k * p.Do * p.Ho * p.Wo;
+  if (r.kern == Kern::Patch || r.kern == Kern::TPatch) {
+    // igemm_k2p / igemm_k2t: in deterministic mode one slab per frame-range / item-range split
+    const bool spatial = r.kern == Kern::Patch;
+    int ns_max = cu_count() / (spatial ? cdiv(d.c, 32) * cdiv(d.k, WP_BM) : cdiv(d.c, WP_BM) * cdiv(d.k, 64));
     ns_max = ns_max < 1 ? 1 : (ns_max > DET_MAX_SPLITS ? DET_MAX_SPLITS : ns_max);
-    const size_t slabs_bytes_p = slab_al * (det ? ns_max : 1);
-    unsigned* cells_p = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + slabs_bytes_p);
-    if (hipMemsetAsync(dwp, 0, slabs_bytes_p + 256, s) != hipSuccess) return fail("hipMemsetAsync failed%s", "");
-    const size_t nx = (size_t)d.n * d.c * d.d * d.h * d.w, ny = (size_t)d.n * d.k * p.Do * p.Ho * p.Wo;
-    if (x_absmax == nullptr) hipLaunchKernelGGL(absmax_kernel, dim3(absmax_grid(nx)), dim3(256), 0, s, x, nx, cells_p);
-    if (dy_absmax == nullptr) hipLaunchKernelGGL(absmax_kernel, dim3(absmax_grid(ny)), dim3(256), 0, s, dy, ny, cells_p + 1);
-    const unsigned* xc = x_absmax != nullptr ? x_absmax : cells_p;
-    const unsigned* dyc = dy_absmax != nullptr ? dy_absmax : cells_p + 1;
-    int nslabs = 1;
-    run_k2p(s, d, p, x, dy, dwp, xc, dyc, det, det_stride_p, &nslabs);
+    const size_t slabs_bytes = slab_al * (det ? ns_max : 1);
+    unsigned* cells = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + slabs_bytes);
+    if (hipMemsetAsync(dwp, 0, slabs_bytes + 256, s) != hipSuccess) return fail("hipMemsetAsync failed%s", "");
+    const unsigned* xc = operand_cell(s, x_absmax, x, nx, cells, nullptr);
+    const unsigned* dyc = operand_cell(s, dy_absmax, dy, ny, cells + 1, nullptr);
+    const int nslabs = spatial ? run_k2p(s, d, p, x, dy, dwp, xc, dyc, det, det_stride)
+                               : run_k2t(s, d, p, x, dy, dwp, xc, dyc, det, det_stride, ia);
     CSTP_LAUNCH_CHECK();
-    const size_t tot_p = (size_t)d.k * d.c * p.ntaps;
-    hipLaunchKernelGGL(unpack_wgrad_kernel, dim3(pack_grid(tot_p)), dim3(256), 0, s, dwp, dw, d.k, d.c, p.ntaps, p.w_Cp, p.w_Jp,
-                       xc, dyc, nslabs, det_stride_p, accumulate ? 1 : 0);
+    unpack_wgrad(s, d, p, dwp, dw, xc, dyc, nslabs, det_stride, c.accumulate);
     CSTP_LAUNCH_CHECK();
     return 0;
   }
-  if (p.w_tpatch && (ia.ss == nullptr || (ia.groups <= 2 && x_absmax != nullptr))) {
-    // igemm_k2t: the temporal layers, both operands staged once (AFF: the transform of x inside; x_absmax is then T(x)'s)
-    const size_t det_stride_p = det ? slab_al / sizeof(float) : 0;
-    int ns_max = cu_count() / (cdiv(d.c, WP_BM) * cdiv(d.k, 64));
-    ns_max = ns_max < 1 ? 1 : (ns_max > DET_MAX_SPLITS ? DET_MAX_SPLITS : ns_max);
-    const size_t slabs_bytes_p = slab_al * (det ? ns_max : 1);
-    unsigned* cells_p = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + slabs_bytes_p);
-    if (hipMemsetAsync(dwp, 0, slabs_bytes_p + 256, s) != hipSuccess) return fail("hipMemsetAsync failed%s", "");
-    const size_t nx = (size_t)d.n * d.c * d.d * d.h * d.w, ny = (size_t)d.n * d.k * p.Do * p.Ho * p.Wo;
-    if (x_absmax == nullptr) hipLaunchKernelGGL(absmax_kernel, dim3(absmax_grid(nx)), dim3(256), 0, s, x, nx, cells_p);
-    if (dy_absmax == nullptr) hipLaunchKernelGGL(absmax_kernel, dim3(absmax_grid(ny)), dim3(256), 0, s, dy, ny, cells_p + 1);
-    const unsigned* xc = x_absmax != nullptr ? x_absmax : cells_p;
-    const unsigned* dyc = dy_absmax != nullptr ? dy_absmax : cells_p + 1;
-    int nslabs = 1;
-    run_k2t(s, d, p, x, dy, dwp, xc, dyc, det, det_stride_p, &nslabs, ia.ss, ia.npg, ia.groups, ia.relu);
-    CSTP_LAUNCH_CHECK();
-    const size_t tot_p = (size_t)d.k * d.c * p.ntaps;
-    hipLaunchKernelGGL(unpack_wgrad_kernel, dim3(pack_grid(tot_p)), dim3(256), 0, s, dwp, dw, d.k, d.c, p.ntaps, p.w_Cp, p.w_Jp,
-                       xc, dyc, nslabs, det_stride_p, accumulate ? 1 : 0);
-    CSTP_LAUNCH_CHECK();
-    return 0;
-  }
-  // the fused input transform: on the f16-pair gather kernel (igemm_k2s<.., AFF>) where aff_split_ok, else the native kernel
-  // with its analytic tile
-  const bool aff_split = ia.ss != nullptr && p.w_split && !p.w_straddle && aff_split_ok(d, ia, x_absmax, (long)p.Do * p.Ho * p.Wo, 32);
-  const bool w_split = p.w_split && (ia.ss == nullptr || aff_split);
-  if (p.w_split && !w_split) p.w_mt = (CSTP_M16 && d.k > 128 && d.k <= 144) ? 9 : pick_mt(d.k);
+  const bool gather = r.t.sp != 0, stem = r.kern == Kern::GatherStem;
+  const int mt = r.t.mt;
   const int npos = d.n * p.Do * p.Ho * p.Wo;
   const int bkn = CSTP_K2_BKN;
   const int kt_total = cdiv(npos, bkn);
-  const int ntm = w_split ? cdiv(d.k, 16 * p.w_mt) : cdiv(d.k, p.w_mt == 9 ? 144 : 32 * p.w_mt), ntj = cdiv(p.w_Jtot, 128);
-  int splits = cdiv(p.w_blocks, ntm * ntj);
+  const int ntm = r.Mp / wgrad_bm(r.t), ntj = cdiv(p.w_Jtot, 128);
+  int splits = cdiv(256 * r.t.wm, ntm * ntj);
   if (splits > cdiv(kt_total, 256 / bkn)) splits = cdiv(kt_total, 256 / bkn);
   if (det && splits > DET_MAX_SPLITS) splits = DET_MAX_SPLITS;
   if (splits < 1) splits = 1;
   const int kt_per = cdiv(kt_total, splits);
   splits = cdiv(kt_total, kt_per);
-  // one slab filled by atomics, or (deterministic) one slab per split; the absmax cells sit in the workspace tail
-  // (the absmax cells of the 2xf16-split kernel sit right behind the slab(s), 256-byte aligned, and are zeroed with them)
-  const size_t det_stride = det ? slab_al / sizeof(float) : 0;
   const size_t slabs_bytes = slab_al * (det ? splits : 1);
   unsigned* cells = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + slabs_bytes);
   if (hipMemsetAsync(dwp, 0, slabs_bytes + 256, s) != hipSuccess) return fail("hipMemsetAsync failed%s", "");
   dim3 grid((unsigned)(align_up((size_t)splits * ntm, 8) * ntj), 1, 1);
-  const bool v4 = ((p.Do * p.Ho * p.Wo) % 4) == 0 && (reinterpret_cast<uintptr_t>(dy) & 15) == 0;
-#define CSTP_K2_ARGS p.w_mt, grid, s, g, dy, x, dwp, p.w_Jtot, p.w_Jp, kt_total, kt_per, ntm, ntj, splits, ia.ss, ia.npg, ia.groups, ia.relu, det_stride
-  const bool w_f16 = w_split && split_planes() == 2;
+  const Geom g = conv_geom(d, p, false, p.w_Cp, 0, p.w_Jtot);      // gather from x, reduction over dy positions
+  const bool w_f16 = gather && split_planes() == 2;
   const unsigned* xcell = x_absmax != nullptr ? x_absmax : cells;
   const unsigned* dycell = dy_absmax != nullptr ? dy_absmax : cells + 1;
-  if (w_split && p.w_straddle) {
-    // the stem: zero-padded copy of x behind the slab(s) + cells (its absmax is the pad kernel's by-product), columns (tap, c)
-    const int Dq = d.d + 2 * d.pt, Hq = d.h + 2 * d.ph, Wq = d.w + 2 * d.pw;
+#define CSTP_K2S_PICK(K_) do { if (mt == 9) K_(9); else if (mt == 4) K_(4); else K_(8); } while (0)
+  if (stem) {
+    // the zero-padded copy of x behind the slab(s) + cells (its absmax is the pad kernel's by-product)
     float* xp = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + slabs_bytes + 256);
-    const int nrows = d.n * d.c * Dq * Hq;
-    const int pgrid = nrows / 4 < 2048 ? (nrows + 3) / 4 : 2048;
-    hipLaunchKernelGGL(pad_input_kernel, dim3(pgrid), dim3(256), 0, s, x, xp, cells, d.n * d.c, d.d, d.h, d.w, d.pt, d.ph, d.pw);
-    const size_t ny = (size_t)d.n * d.k * p.Do * p.Ho * p.Wo;
-    if (dy_absmax == nullptr) hipLaunchKernelGGL(absmax_kernel, dim3(absmax_grid(ny)), dim3(256), 0, s, dy, ny, cells + 1);
-    Geom gs = g;
-    gs.Ds = Dq; gs.Hs = Hq; gs.Ws = Wq; gs.pt = 0; gs.ph = 0; gs.pw = 0; gs.Cp = d.c;
+    pad_stem_input(s, d, x, xp, cells);
+    xcell = cells;
+    operand_cell(s, dy_absmax, dy, ny, cells + 1, nullptr);
+    const Geom gs = stem_geom(g, d);
 #define CSTP_K2S_STR(MT_) \
   hipLaunchKernelGGL((igemm_k2s<MT_, 2, true>), grid, dim3(512), 0, s, gs, dy, xp, dwp, p.w_Jtot, p.w_Jp, kt_total, kt_per, ntm, ntj, splits, cells, dycell, det_stride, (const float2*)nullptr, 1, 1, 0)
-    if (p.w_mt == 9) CSTP_K2S_STR(9); else if (p.w_mt == 4) CSTP_K2S_STR(4); else CSTP_K2S_STR(8);
+    CSTP_K2S_PICK(CSTP_K2S_STR);
 #undef CSTP_K2S_STR
-    CSTP_LAUNCH_CHECK();
-    const size_t tot_s = (size_t)d.k * d.c * p.ntaps;
-    hipLaunchKernelGGL(unpack_wgrad_kernel, dim3(pack_grid(tot_s)), dim3(256), 0, s, dwp, dw, d.k, d.c, p.ntaps, p.w_Cp, p.w_Jp,
-                       cells, dycell, det ? splits : 1, det_stride, accumulate ? 1 : 0);
-    CSTP_LAUNCH_CHECK();
-    return 0;
-  }
-  if (w_split) {
-#define CSTP_K2S(MT_, NP_) \
-  hipLaunchKernelGGL((igemm_k2s<MT_, NP_>), grid, dim3(512), 0, s, g, dy, x, dwp, p.w_Jtot, p.w_Jp, kt_total, kt_per, ntm, ntj, splits, xcell, dycell, det_stride, (const float2*)nullptr, 1, 1, 0)
+  } else if (gather) {
+#define CSTP_K2S_F16(MT_) \
+  hipLaunchKernelGGL((igemm_k2s<MT_, 2>), grid, dim3(512), 0, s, g, dy, x, dwp, p.w_Jtot, p.w_Jp, kt_total, kt_per, ntm, ntj, splits, xcell, dycell, det_stride, (const float2*)nullptr, 1, 1, 0)
+#define CSTP_K2S_B16(MT_) \
+  hipLaunchKernelGGL((igemm_k2s<MT_, 3>), grid, dim3(512), 0, s, g, dy, x, dwp, p.w_Jtot, p.w_Jp, kt_total, kt_per, ntm, ntj, splits, xcell, dycell, det_stride, (const float2*)nullptr, 1, 1, 0)
 #define CSTP_K2S_AFF(MT_) \
   hipLaunchKernelGGL((igemm_k2s<MT_, 2, false, true>), grid, dim3(512), 0, s, g, dy, x, dwp, p.w_Jtot, p.w_Jp, kt_total, kt_per, ntm, ntj, splits, xcell, dycell, det_stride, ia.ss, ia.npg * p.Do * p.Ho * p.Wo, ia.groups, ia.relu)
     if (w_f16) {
-      const size_t nx = (size_t)d.n * d.c * d.d * d.h * d.w, ny = (size_t)d.n * d.k * p.Do * p.Ho * p.Wo;
-      if (x_absmax == nullptr) hipLaunchKernelGGL(absmax_kernel, dim3(absmax_grid(nx)), dim3(256), 0, s, x, nx, cells);
-      if (dy_absmax == nullptr) hipLaunchKernelGGL(absmax_kernel, dim3(absmax_grid(ny)), dim3(256), 0, s, dy, ny, cells + 1);
-      if (aff_split) { if (p.w_mt == 9) CSTP_K2S_AFF(9); else if (p.w_mt == 4) CSTP_K2S_AFF(4); else CSTP_K2S_AFF(8); }
-      else if (p.w_mt == 9) CSTP_K2S(9, 2); else if (p.w_mt == 4) CSTP_K2S(4, 2); else CSTP_K2S(8, 2);
+      operand_cell(s, x_absmax, x, nx, cells, nullptr);
+      operand_cell(s, dy_absmax, dy, ny, cells + 1, nullptr);
+      if (r.fused) CSTP_K2S_PICK(CSTP_K2S_AFF); else CSTP_K2S_PICK(CSTP_K2S_F16);
     } else {
-      if (p.w_mt == 9) CSTP_K2S(9, 3); else if (p.w_mt == 4) CSTP_K2S(4, 3); else CSTP_K2S(8, 3);
+      CSTP_K2S_PICK(CSTP_K2S_B16);
     }
-#undef CSTP_K2S
+#undef CSTP_K2S_F16
+#undef CSTP_K2S_B16
 #undef CSTP_K2S_AFF
-  } else if (p.w_straddle) {
-    if (v4) launch_k2<true, true, CSTP_K2_BKN, false>(CSTP_K2_ARGS);
-    else launch_k2<true, false, CSTP_K2_BKN, false>(CSTP_K2_ARGS);
-  } else if (ia.ss) {
-    if (v4) launch_k2<false, true, CSTP_K2_BKN, true>(CSTP_K2_ARGS);
-    else launch_k2<false, false, CSTP_K2_BKN, true>(CSTP_K2_ARGS);
   } else {
-    if (v4) launch_k2<false, true, CSTP_K2_BKN, false>(CSTP_K2_ARGS);
-    else launch_k2<false, false, CSTP_K2_BKN, false>(CSTP_K2_ARGS);
-  }
+    const bool v4 = ((p.Do * p.Ho * p.Wo) % 4) == 0 && (reinterpret_cast<uintptr_t>(dy) & 15) == 0;
+#define CSTP_K2_ARGS mt, grid, s, g, dy, x, dwp, p.w_Jtot, p.w_Jp, kt_total, kt_per, ntm, ntj, splits, ia.ss, ia.npg, ia.groups, ia.relu, det_stride
+    if (r.kern == Kern::NativeStraddle) {
+      if (v4) launch_k2<true, true, CSTP_K2_BKN, false>(CSTP_K2_ARGS);
+      else launch_k2<true, false, CSTP_K2_BKN, false>(CSTP_K2_ARGS);
+    } else if (r.kern == Kern::NativeXform) {
+      if (v4) launch_k2<false, true, CSTP_K2_BKN, true>(CSTP_K2_ARGS);
+      else launch_k2<false, false, CSTP_K2_BKN, true>(CSTP_K2_ARGS);
+    } else {
+      if (v4) launch_k2<false, true, CSTP_K2_BKN, false>(CSTP_K2_ARGS);
+      else launch_k2<false, false, CSTP_K2_BKN, false>(CSTP_K2_ARGS);
+    }
 #undef CSTP_K2_ARGS
+  }
+#undef CSTP_K2S_PICK
   CSTP_LAUNCH_CHECK();
-  const size_t tot = (size_t)d.k * d.c * p.ntaps;
-  hipLaunchKernelGGL(unpack_wgrad_kernel, dim3(pack_grid(tot)), dim3(256), 0, s, dwp, dw, d.k, d.c, p.ntaps, p.w_Cp, p.w_Jp,
-                     w_f16 ? xcell : nullptr, w_f16 ? dycell : nullptr, det ? splits : 1, det_stride, accumulate ? 1 : 0);
+  unpack_wgrad(s, d, p, dwp, dw, w_f16 ? xcell : nullptr, w_f16 ? dycell : nullptr, det ? splits : 1, det_stride, c.accumulate);
   CSTP_LAUNCH_CHECK();
   return 0;
 }
@@ -2011,28 +2031,21 @@ extern "C" int cstp_conv3d_query_tile(const cstp_conv_desc* desc, int32_t mode, 
   CSTP_REQUIRE(desc && out4, "null argument");
   CSTP_REQUIRE(mode >= 0 && mode <= 3, "mode must be 0 (forward), 1 (backward_data), 2 (backward_weight) or 3 (forward with an in_affine)");
   ConvPlan p;
-  CSTP_REQUIRE(make_plan(*desc, p, mode == 3), "invalid conv descriptor");
-  if (mode == 3) mode = 0;
-  if (mode == 2 && p.w_patch) {       // igemm_k2p: 144 rows x (32 channels x 9 taps), f16 pair
-    out4[0] = WP_BM; out4[1] = 288; out4[2] = 2; out4[3] = 0;
-    return 0;
+  CSTP_REQUIRE(make_plan(*desc, p), "invalid conv descriptor");
+  const cstp_conv_desc& d = *desc;
+  const Route r = mode == 2 ? route_wgrad(d, p, query_facts(0, 0)) : mode == 1 ? route_dgrad(d, p, query_facts(0, 0))
+                                                                                 : query_forward(d, p, mode == 3 ? 1 : 0, 0);
+  if (mode == 2 && (r.kern == Kern::Patch || r.kern == Kern::TPatch)) {
+    // igemm_k2p: 144 rows x (32 channels x 9 taps); igemm_k2t: 144 x-channels x (64 dY channels x 3 taps); f16 pair
+    out4[0] = WP_BM; out4[1] = r.kern == Kern::Patch ? 288 : 192; out4[2] = 2; out4[3] = 0;
+  } else if (mode == 2) {
+    out4[0] = wgrad_bm(r.t); out4[1] = 128; out4[2] = r.t.sp ? split_planes() : 0; out4[3] = r.t.wm;
+  } else {
+    out4[0] = tile_bm(r.t);
+    out4[1] = tile_bn(r.t);
+    out4[2] = r.t.sp ? split_planes() : 0;       // (the patch kernels and the stems' straddle mode: f16 pair only -- the routes)
+    out4[3] = r.t.tpb == 2 ? 2 : 1;
   }
-  if (mode == 2 && p.w_tpatch) {      // igemm_k2t: 144 x-channels x (64 dY channels x 3 taps), f16 pair
-    out4[0] = WP_BM; out4[1] = 192; out4[2] = 2; out4[3] = 0;
-    return 0;
-  }
-  if (mode == 2) {
-    out4[0] = p.w_split ? 16 * p.w_mt : (p.w_mt == 9 ? 144 : 32 * p.w_mt);
-    out4[1] = 128;
-    out4[2] = p.w_split ? split_planes() : 0;
-    out4[3] = p.w_blocks / 256;
-    return 0;
-  }
-  const Tile& t = mode == 0 ? p.f_t : p.d_t;
-  out4[0] = tile_bm(t);
-  out4[1] = tile_bn(t);
-  out4[2] = t.sp ? split_planes() : 0;       // (the patch kernel and the stems' straddle mode: f16 pair only -- make_plan)
-  out4[3] = t.tpb == 2 ? 2 : 1;
   return 0;
 }
 
@@ -2129,97 +2142,62 @@ extern "C" int cstp_conv3d_autotune(void* stream, const cstp_conv_desc* desc, in
     if (mode == 2) hipLaunchKernelGGL(absmax_kernel, dim3(absmax_grid(ny)), dim3(256), 0, s0, w, ny, tune_cells + 1);
     CSTP_LAUNCH_CHECK();
   }
-  if (mode == 2) {
-    // weight gradient (src = x, w = dy, out = dw): row-tile height x split-K block target
-    const bool stem = d.c < 8;
-    Tile wc[24];
-    int nw = 0;
-    const int base = pick_mt(d.k);
-    const bool allow_split2 = !native_only();
-    for (int blocks = 4; blocks <= 16; blocks *= 2) {
-      wc[nw++] = Tile{base, blocks, 0};
-      if (!stem && d.k > 128 && d.k <= 144) wc[nw++] = Tile{9, blocks, 1};
-      for (int mt = 2; mt <= 5; ++mt)
-        if (mt != base && cdiv(d.k, 32 * mt) * 32 * mt <= cdiv(d.k, 32 * base) * 32 * base + 16 && nw < 15) wc[nw++] = Tile{mt, blocks, 0};
-    }
-    if (allow_split2 && stem && split_planes() == 2 && d.k >= 48) {      // the stems on igemm_k2s<.., STR> (f16 pair)
-      int smt = 4, pad = cdiv(d.k, 64) * 64 - d.k;
-      if (cdiv(d.k, 128) * 128 - d.k <= pad) { smt = 8; pad = cdiv(d.k, 128) * 128 - d.k; }
-      if (cdiv(d.k, 144) * 144 - d.k < pad) smt = 9;
-      for (int blocks = 4; blocks <= 16; blocks *= 2) wc[nw++] = Tile{smt, blocks, 0, 0, 1};
-    }
-    if (allow_split2 && !stem && d.k >= 48) {      // igemm_k2s: 64- / 128- / 144-row tiles, whichever pads the rows least
-      int smt = 4, pad = cdiv(d.k, 64) * 64 - d.k;
-      if (cdiv(d.k, 128) * 128 - d.k <= pad) { smt = 8; pad = cdiv(d.k, 128) * 128 - d.k; }
-      if (cdiv(d.k, 144) * 144 - d.k < pad) smt = 9;
-      for (int blocks = 4; blocks <= 16; blocks *= 2) wc[nw++] = Tile{smt, blocks, 0, 0, 1};
-    }
-    if (allow_split2 && !stem && (wpatch_geom_ok(d) || twpatch_geom_ok(d))) wc[nw++] = Tile{9, 1, 0, 0, 2};      // igemm_k2p / igemm_k2t
-    hipStream_t s2 = as_stream(stream);
-    hipEvent_t a0, a1;
-    if (hipEventCreate(&a0) != hipSuccess || hipEventCreate(&a1) != hipSuccess) return fail("hipEventCreate failed%s", "");
-    float bms = 1e30f;
-    int bi = -1, rc2 = 0;
-    for (int i = 0; i < nw && rc2 == 0; ++i) {
-      g_force_tile = &wc[i];
-      g_force_mode = 2;
-      for (int it = -1; it < iters && rc2 == 0; ++it) {
-        if (it == 0) (void)hipEventRecord(a0, s2);
-        rc2 = cstp_conv3d_backward_weight_am(stream, desc, src, nullptr, w, out, ws, ws_bytes, tune_cells, tune_cells + 1);
-      }
-      g_force_tile = nullptr;
-      if (rc2 != 0) break;
-      (void)hipEventRecord(a1, s2);
-      if (hipEventSynchronize(a1) != hipSuccess) { rc2 = fail("hipEventSynchronize failed%s", ""); break; }
-      float ms = 0.f;
-      (void)hipEventElapsedTime(&ms, a0, a1);
-      if (ms < bms) { bms = ms; bi = i; }
-    }
-    g_force_tile = nullptr;
-    (void)hipEventDestroy(a0);
-    (void)hipEventDestroy(a1);
-    if (rc2 != 0) return rc2;
-    CSTP_REQUIRE(bi >= 0, "no weight-gradient candidate ran");
-    std::lock_guard<std::mutex> lk(g_tune_mu);
-    g_tuned[tune_key(d, 2)] = wc[bi];
-    return 0;
-  }
-  const int M = mode == 0 ? d.k : d.c;
-  const bool straddle = (mode == 0 && d.c < 8);
+  const int M = mode == 1 ? d.c : d.k;
+  const bool straddle = d.c < 8;
+  const bool allow_split = !native_only();      // the split kernels (fp32-equivalent products on the 16-bit matrix cores), unless CSTP_GEMM=f32
   Tile cand[44] = {{1, 1, 0, 1}, {2, 1, 0, 1}, {3, 1, 0, 1}, {4, 1, 0, 1}, {5, 1, 0, 1}, {1, 2, 0, 1}, {2, 2, 0, 1}, {1, 4, 0, 1},
                    {9, 1, 1, 1}};
-  int ncand = (CSTP_M16 && !straddle && M > 128 && M <= 144) ? 9 : 8;
-  if (!straddle) {       // the same tiles with two K-tiles per barrier
-    const int n1 = ncand;
-    for (int i = 0; i < n1; ++i) { cand[ncand] = cand[i]; cand[ncand].tpb = 2; ++ncand; }
-  }
-  // the 3xbf16-split kernels (fp32-equivalent products on the bf16 matrix cores), unless CSTP_GEMM=f32
-  const bool allow_split = !native_only();
-  if (allow_split && !straddle && d.kt * d.kh * d.kw <= 27) {
-    // row-tile heights 32..144; keep those that pad M by at most ~1/8 (and the two smallest paddings regardless)
-    static const int smt[] = {2, 3, 4, 5, 6, 8, 9};
-    int best_pad = 1 << 30;
-    for (int mt : smt) { const int pad = cdiv(M, 16 * mt) * 16 * mt - M; if (pad < best_pad) best_pad = pad; }
-    for (int mt : smt) {
-      const int pad = cdiv(M, 16 * mt) * 16 * mt - M;
-      if ((pad <= best_pad + M / 8) && ncand < 38) {
-        cand[ncand++] = Tile{mt, 1, 0, 1, 1};
-        if (mt >= 8) cand[ncand++] = Tile{mt, 2, 0, 1, 1};      // 256-column tile
+  int ncand = 0;
+  if (mode == 2) {
+    // weight gradient (src = x, w = dy, out = dw): row-tile height x split-K block target
+    const int base = pick_mt(d.k);
+    for (int blocks = 4; blocks <= 16; blocks *= 2) {
+      cand[ncand++] = Tile{base, blocks, 0};
+      if (!straddle && d.k > 128 && d.k <= 144) cand[ncand++] = Tile{9, blocks, 1};
+      for (int mt = 2; mt <= 5; ++mt)
+        if (mt != base && cdiv(d.k, 32 * mt) * 32 * mt <= cdiv(d.k, 32 * base) * 32 * base + 16 && ncand < 15) cand[ncand++] = Tile{mt, blocks, 0};
+    }
+    // igemm_k2s: 64- / 128- / 144-row tiles, whichever pads the rows least (the stems on igemm_k2s<.., STR>: f16 pair only)
+    if (allow_split && d.k >= 48 && (!straddle || split_planes() == 2)) {
+      int smt = 4, pad = cdiv(d.k, 64) * 64 - d.k;
+      if (cdiv(d.k, 128) * 128 - d.k <= pad) { smt = 8; pad = cdiv(d.k, 128) * 128 - d.k; }
+      if (cdiv(d.k, 144) * 144 - d.k < pad) smt = 9;
+      for (int blocks = 4; blocks <= 16; blocks *= 2) cand[ncand++] = Tile{smt, blocks, 0, 0, 1};
+    }
+    if (allow_split && !straddle && (wpatch_geom_ok(d) || twpatch_geom_ok(d))) cand[ncand++] = Tile{9, 1, 0, 0, 2};      // igemm_k2p / igemm_k2t
+  } else {
+    const bool stem = mode == 0 && straddle;
+    ncand = (CSTP_M16 && !stem && M > 128 && M <= 144) ? 9 : 8;
+    if (!stem) {       // the same tiles with two K-tiles per barrier
+      const int n1 = ncand;
+      for (int i = 0; i < n1; ++i) { cand[ncand] = cand[i]; cand[ncand].tpb = 2; ++ncand; }
+    }
+    if (allow_split && !stem && d.kt * d.kh * d.kw <= 27) {
+      // row-tile heights 32..144; keep those that pad M by at most ~1/8 (and the two smallest paddings regardless)
+      static const int smt[] = {2, 3, 4, 5, 6, 8, 9};
+      int best_pad = 1 << 30;
+      for (int mt : smt) { const int pad = cdiv(M, 16 * mt) * 16 * mt - M; if (pad < best_pad) best_pad = pad; }
+      for (int mt : smt) {
+        const int pad = cdiv(M, 16 * mt) * 16 * mt - M;
+        if ((pad <= best_pad + M / 8) && ncand < 38) {
+          cand[ncand++] = Tile{mt, 1, 0, 1, 1};
+          if (mt >= 8) cand[ncand++] = Tile{mt, 2, 0, 1, 1};      // 256-column tile
+        }
       }
     }
-  }
-  if (allow_split && straddle && split_planes() == 2) {      // the stems: split tiles in straddle mode, 64 / 80 / 96 rows
-    for (int mt = 4; mt <= 6; ++mt)
-      if (cdiv(M, 16 * mt) * 16 * mt - M <= 16 + M / 8 && ncand < 40) cand[ncand++] = Tile{mt, 1, 0, 1, 1};
-  }
-  if (allow_split && (patch_geom_ok(d) || tpatch_geom_ok(d))) {       // the LDS-resident-patch kernels: row blocks of 64 / 128 / 144
-    static const int pmt[] = {4, 8, 9};
-    int best_pad = 1 << 30;
-    for (int mt : pmt) { const int pad = cdiv(M, 16 * mt) * 16 * mt - M; if (pad < best_pad) best_pad = pad; }
-    for (int mt : pmt)
-      if (cdiv(M, 16 * mt) * 16 * mt - M <= best_pad + M / 8 && ncand < 40) cand[ncand++] = Tile{mt, 1, 0, 1, 2};
-    // the weight-resident temporal forward kernel igemm_k1w (64 rows, <= 15 K-tiles)
-    if (mode == 0 && tpatch_geom_ok(d) && k1w_fits(d.k, d.c) && ncand < 41) cand[ncand++] = Tile{4, 2, 0, 1, 2};
+    if (allow_split && stem && split_planes() == 2) {      // the stems: split tiles in straddle mode, 64 / 80 / 96 rows
+      for (int mt = 4; mt <= 6; ++mt)
+        if (cdiv(M, 16 * mt) * 16 * mt - M <= 16 + M / 8 && ncand < 40) cand[ncand++] = Tile{mt, 1, 0, 1, 1};
+    }
+    if (allow_split && (patch_geom_ok(d) || tpatch_geom_ok(d))) {       // the LDS-resident-patch kernels: row blocks of 64 / 128 / 144
+      static const int pmt[] = {4, 8, 9};
+      int best_pad = 1 << 30;
+      for (int mt : pmt) { const int pad = cdiv(M, 16 * mt) * 16 * mt - M; if (pad < best_pad) best_pad = pad; }
+      for (int mt : pmt)
+        if (cdiv(M, 16 * mt) * 16 * mt - M <= best_pad + M / 8 && ncand < 40) cand[ncand++] = Tile{mt, 1, 0, 1, 2};
+      // the weight-resident temporal forward kernel igemm_k1w (64 rows, <= 15 K-tiles)
+      if (mode == 0 && tpatch_geom_ok(d) && k1w_fits(d.k, d.c) && ncand < 41) cand[ncand++] = Tile{4, 2, 0, 1, 2};
+    }
   }
   hipStream_t s = as_stream(stream);
   hipEvent_t e0, e1;
@@ -2227,13 +2205,14 @@ extern "C" int cstp_conv3d_autotune(void* stream, const cstp_conv_desc* desc, in
   float best_ms = 1e30f;
   int best = -1, rc = 0;
   for (int i = 0; i < ncand && rc == 0; ++i) {
-    if (cdiv(M, tile_bm(cand[i])) * tile_bm(cand[i]) > M + 160) continue;
+    if (mode != 2 && cdiv(M, tile_bm(cand[i])) * tile_bm(cand[i]) > M + 160) continue;
     g_force_tile = &cand[i];
     g_force_mode = mode;
     for (int it = -1; it < iters && rc == 0; ++it) {      // it == -1: untimed warm-up launch
       if (it == 0) (void)hipEventRecord(e0, s);
       rc = mode == 0 ? cstp_conv3d_forward_am(stream, desc, src, w, nullptr, nullptr, out, ws, ws_bytes, tune_cells)
-                     : cstp_conv3d_backward_data_am(stream, desc, src, w, out, ws, ws_bytes, tune_cells);
+         : mode == 1 ? cstp_conv3d_backward_data_am(stream, desc, src, w, out, ws, ws_bytes, tune_cells)
+                     : cstp_conv3d_backward_weight_am(stream, desc, src, nullptr, w, out, ws, ws_bytes, tune_cells, tune_cells + 1);
     }
     g_force_tile = nullptr;
     if (rc != 0) break;
@@ -2250,7 +2229,7 @@ extern "C" int cstp_conv3d_autotune(void* stream, const cstp_conv_desc* desc, in
       const double ybytes = 4.0 * d.n * d.k * (double)d.d * d.h * d.w;
       ms += (float)(iters * ybytes / 5.5e9);
     }
-    {
+    if (mode != 2) {
       static const bool verbose = getenv("CSTP_TUNE_VERBOSE") != nullptr;     // developer knob: the ranking as the tuner saw it
       if (verbose)
         fprintf(stderr, "cstp tune mode %d [%d %d %d %d %d -> %d, %dx%dx%d]: tile {sp %d, mt %d, wm %d, tpb %d}  %.4f ms per launch (as ranked)\n",
@@ -2264,9 +2243,7 @@ extern "C" int cstp_conv3d_autotune(void* stream, const cstp_conv_desc* desc, in
   (void)hipEventDestroy(e1);
   if (rc != 0) return rc;
   CSTP_REQUIRE(best >= 0, "no tile candidate ran");
-  {
-    std::lock_guard<std::mutex> lk(g_tune_mu);
-    g_tuned[tune_key(d, mode)] = cand[best];
-  }
+  std::lock_guard<std::mutex> lk(g_tune_mu);
+  g_tuned[tune_key(d, mode)] = cand[best];
   return 0;
 }

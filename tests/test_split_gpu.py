@@ -40,20 +40,21 @@ def terms(request):
     ops.set_split_terms(0)
 
 
-def _run(name, tiles, scale_x=1.0, scale_w=1.0, scale_dy=1.0, tol=TOL):
+def _run(name, tiles, scale_x=1.0, scale_w=1.0, scale_dy=1.0, tol=TOL, bias=False):
     """tiles: {mode: tile4}.  Returns nothing; asserts parity of y, dx, dw."""
     from cstp_amd import ops
     xs, k, ks, st, pd = GEOMS[name]
     x = (_rand(xs, 1) * scale_x).requires_grad_(True)
     w = (_rand((k, xs[1]) + ks, 2) * 0.2 * scale_w).requires_grad_(True)
-    y = F.conv3d(x, w, None, st, pd)
+    b = _rand((k,), 4) if bias else None
+    y = F.conv3d(x, w, b, st, pd)
     dy = _rand(y.shape, 3) * scale_dy
     y.backward(dy)
     for mode, tile in tiles.items():
         ops.set_conv_tile(xs, w.shape, st, pd, mode, tile)
     xg = x.detach().float().cuda().requires_grad_(True)
     wg = w.detach().float().cuda().requires_grad_(True)
-    yg = ops.conv3d(xg, wg, None, st, pd)
+    yg = ops.conv3d(xg, wg, b.float().cuda() if bias else None, st, pd)
     yg.backward(dy.float().cuda())
     assert rel_err(yg, y) < tol, ("forward", name, tiles)
     assert rel_err(xg.grad, x.grad) < tol, ("backward_data", name, tiles)
@@ -275,10 +276,17 @@ def test_patch_kernel_scale_invariance_and_zero_operands():
 
 
 def test_patch_tile_is_refused_where_the_kernel_does_not_apply():
-    """A patch tile pinned on a strided / temporal / bf16-triple call falls back to another kernel at call time."""
+    """A patch tile pinned on a strided / temporal / bf16-triple call, or on a call with a bias (the spatial and the temporal
+    patch layer: the 144-row gather tile), falls back to another kernel at call time."""
     from cstp_amd import ops
     for name in ("S2s", "T1"):
         _run(name, {0: (2, 9, 0, 0), 1: (2, 4, 0, 0), 2: (0, 2, 8, 0)})
+    GEOMS["_tpatch"] = ((2, 48, 8, 14, 14), 64, (3, 1, 1), (1, 1, 1), (1, 0, 0))
+    try:
+        for name in ("S1", "_tpatch"):
+            _run(name, {0: (2, 9, 0, 0), 1: (2, 4, 0, 0), 2: (0, 2, 8, 0)}, bias=True)
+    finally:
+        del GEOMS["_tpatch"]
     xs, k = PATCH_GEOMS["S1"]
     GEOMS["_patch"] = (xs, k, (1, 3, 3), (1, 1, 1), (0, 1, 1))
     ops.set_split_terms(3)
