@@ -175,6 +175,9 @@ SIGNATURES = {
     "cstp_bnrelu_concat_eval": (c_int32, [_P, POINTER(BncBranch), c_int32, c_int32, c_int32, c_float, _P, _P, _P]),
     "cstp_bnrelu_concat_backward": (c_int32, [_P, POINTER(BncBranch), c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P,
                                               c_size_t, c_int32]),
+    # retrieval: streaming similarity top-k (csrc/retrieve.hip)
+    "cstp_simtopk_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "cstp_simtopk": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, c_size_t]),
 }
 
 _lib = None

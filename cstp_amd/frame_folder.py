@@ -203,14 +203,16 @@ class _FolderSource:
 
     _SALT = {"train": 11, "val": 23, "test": 37}
 
-    def __init__(self, device, frame_dir, annotation_path, split, data_type, sample_duration, sample_size, seed, n_workers):
+    def __init__(self, device, frame_dir, annotation_path, split, data_type, sample_duration, sample_size, seed, n_workers,
+                 list_from=None):
         if data_type not in self._SALT:
             raise ValueError("data_type %r" % (data_type,))
         self.device, self.data_type = torch.device(device), data_type
         self.t, self.size, self.seed = sample_duration, sample_size, seed
         self.threads = decode_threads(n_workers)
         self.frame_dir, self.annotation_path, self.split = frame_dir, annotation_path, split
-        self.data = read_list(annotation_path, frame_dir, data_type, split)
+        self.list_from = data_type if list_from is None else list_from
+        self.data = read_list(annotation_path, frame_dir, self.list_from, split)
         self._stager = None
         self._pending = None          # (key, staged request) of the prefetched batch
 
@@ -326,17 +328,23 @@ class FramePairFolder(_FolderSource):
 class FrameLabelledFolder(_FolderSource):
     """UcfFineTune on the GPU clip pipeline: ``batch(indices, epoch)`` and ``video(index)`` behave as ``GpuLabelledVideos``'
     do, from the JPEG frames of the listed videos, under the PIL transform modes 'img' / 'img_val' / 'img_test' (the ``numpy*``
-    modes resize with cv2 and stay refused).  The label is the list's second column as it stands (datasets.py:977)."""
+    modes resize with cv2 and stay refused).  The label is the list's second column as it stands (datasets.py:977).
+    ``list_from="train"`` with data_type 'test' / mode 'img_test' reads the TRAIN list as whole-video test items: the gallery of
+    nearest-neighbour retrieval (cstp_amd.retrieval); by default the list follows data_type."""
 
     def __init__(self, device, frame_dir, annotation_path, split=1, data_type="train", mode="img", sample_duration=16,
-                 sample_size=112, pb_rate=4, seed=1, n_workers=4):
+                 sample_size=112, pb_rate=4, seed=1, n_workers=4, list_from=None):
         sampler._check_ft_mode(mode)
         if (data_type == "test") != (mode == "img_test"):
             raise ValueError("data_type %r with transform mode %r: the video test takes 'img_test', train / val take 'img' / "
                              "'img_val'" % (data_type, mode))
         if mode != "img":
             sampler.short_side(sample_size)
-        super().__init__(device, frame_dir, annotation_path, split, data_type, sample_duration, sample_size, seed, n_workers)
+        if list_from is not None and (list_from not in ("train", "test") or data_type != "test"):
+            raise ValueError("list_from %r with data_type %r: only the video test reads another list ('train' | 'test')"
+                             % (list_from, data_type))
+        super().__init__(device, frame_dir, annotation_path, split, data_type, sample_duration, sample_size, seed, n_workers,
+                         list_from)
         self.mode, self.pb_rate = mode, pb_rate
         self.labels = [lab for _, lab, _ in self.data]
 
@@ -431,7 +439,7 @@ def build_pretrain(opts, device) -> FramePairFolder:
                            opts.sample_size, opts.manual_seed, opts.n_workers)
 
 
-def build_finetune(opts, device, data_type: str, mode: str) -> FrameLabelledFolder:
+def build_finetune(opts, device, data_type: str, mode: str, list_from=None) -> FrameLabelledFolder:
     """--dataset UcfFineTune from the reference's flags, for 'train' / 'val' / 'test' under ``mode``."""
     return FrameLabelledFolder(device, opts.frame_dir, opts.annotation_path, opts.split, data_type, mode, opts.sample_duration,
-                               opts.sample_size, opts.pb_rate, opts.manual_seed, opts.n_workers)
+                               opts.sample_size, opts.pb_rate, opts.manual_seed, opts.n_workers, list_from)

@@ -15,6 +15,8 @@ is exactly that local BN, so --sync_bn 0/1 select the same arithmetic.  Without 
 nn.DataParallel, which on one device only adds the ``module.`` key prefix; ``SingleDeviceParallel`` keeps that prefix so
 checkpoints are interchangeable between launch modes and with the reference.  New: --model_depth picks the layer sizes;
 ``--task resume`` (undefined model in the reference: neither task list of :44-49 contains it) builds the fine-tune model.
+``--task retrieval`` (no counterpart in the reference) builds the pre-training wrapper on one device, loads the encoder of
+--pretrained_path and returns the model alone in eval mode (``_retrieval_model``; retrieval.py, cstp_amd.retrieval).
 """
 from __future__ import annotations
 
@@ -30,6 +32,7 @@ from .s3dg_byol import get_fine_tuning_parameters as s3dg_fine_tuning_parameters
 
 PRETRAIN_TASKS = ("r_byol", "loss_com")
 FINETUNE_TASKS = ("ft_fc", "ft_all", "scratch", "test", "resume")
+RETRIEVAL_TASKS = ("retrieval",)     # nearest-neighbour retrieval on the encoder feature (cstp_amd.retrieval): no training
 
 
 class SingleDeviceParallel(nn.Module):
@@ -68,12 +71,53 @@ def _load_checkpoint(path, device):
     return torch.load(path, map_location=device)
 
 
+def _build(opts, pretrain):
+    """The wrapper of the named backbone: pre-training (two encoders, predictor, pretext heads) or fine-tune (encoder and
+    classifier)."""
+    if opts.model_name == "r3d_byol":        # models/model.py:65-70: R3DBYOL(pretrain=..., [cls_bn=True,] opts=opts)
+        return R3DBYOL(pretrain=True, opts=opts) if pretrain else R3DBYOL(pretrain=False, cls_bn=True, opts=opts)
+    if opts.model_name == "i3d_byol":        # models/model.py:66-71: I3DBYOL(pretrain=..., opts=opts)
+        return I3DBYOL(pretrain=pretrain, opts=opts)
+    act = getattr(opts, "act_dtype", "fp32") or "fp32"
+    if opts.model_name == "s3d_byol":        # models/model.py:54-59: S3DGBYOL(pretrain=..., gating=True, slow=False, ...)
+        return S3DGBYOL(pretrain=pretrain, gating=True, slow=False, num_classes=opts.n_classes, act_dtype=act)
+    layer_sizes = layer_sizes_for_depth(opts.model_depth)
+    if pretrain:
+        return R21DBYOL(pretrain=True, layer_sizes=layer_sizes, act_dtype=act)
+    return R21DBYOL(pretrain=False, num_classes=opts.n_classes, cls_bn=True, layer_sizes=layer_sizes, act_dtype=act)
+
+
+def _retrieval_model(opts):
+    """--task retrieval: the pre-training wrapper of the named backbone on one device, never under DDP, in eval mode, with the
+    encoder of --pretrained_path.  Only the ``module.online_net.*`` keys matter (pre-training and fine-tune checkpoints name
+    the encoder alike); an ``online_net`` tensor of the model that the checkpoint lacks is an error, since a half-loaded
+    encoder would still produce numbers."""
+    model = _build(opts, True)
+    local_rank = opts.local_rank if getattr(opts, "local_rank", -1) not in (-1, None) else 0
+    torch.cuda.set_device(local_rank)
+    model.cuda(local_rank)
+    model.flatten_parameters()
+    model = SingleDeviceParallel(model)
+    checkpoint = _load_checkpoint(opts.pretrained_path, torch.device("cpu"))
+    arch = getattr(opts, "arch", None)
+    if arch is not None and "arch" in checkpoint:
+        assert (arch in checkpoint["arch"] or checkpoint["arch"] in arch)
+    state = checkpoint["state_dict"]
+    missing = [k for k in model.state_dict() if k.startswith("module.online_net.") and k not in state]
+    if missing:
+        raise ValueError("--pretrained_path %s lacks %d of the encoder's tensors (first: %s): not a checkpoint of %s"
+                         % (opts.pretrained_path, len(missing), missing[0], opts.model_name))
+    model = neq_load_customized(model, state, verbose=False)
+    model.eval()
+    return model
+
+
 def generate_model(opts):
     if opts.model_name not in ("r21d_byol", "r3d_byol", "s3d_byol", "i3d_byol"):
         raise ValueError("Please check the input backbone! (cstp_amd provides model_name=r21d_byol | r3d_byol | s3d_byol | "
                          "i3d_byol, got %r)" % (opts.model_name,))
-    if opts.task not in PRETRAIN_TASKS + FINETUNE_TASKS:
-        raise ValueError("task %r: r21d_byol serves %s" % (opts.task, PRETRAIN_TASKS + FINETUNE_TASKS))
+    if opts.task not in PRETRAIN_TASKS + FINETUNE_TASKS + RETRIEVAL_TASKS:
+        raise ValueError("task %r: r21d_byol serves %s" % (opts.task, PRETRAIN_TASKS + FINETUNE_TASKS + RETRIEVAL_TASKS))
     if opts.model_name == "i3d_byol" and opts.task == "ft_fc":
         # models/BE/i3d_byol.py:17-38 keeps parameters whose name contains 'layer<i>' or 'fc' trainable: I3D has none
         raise ValueError("--task ft_fc with i3d_byol leaves nothing to train: the fine-tune plan matches parameter names "
@@ -84,24 +128,9 @@ def generate_model(opts):
                          "and I3DBYOL has no `classify` for o_type='scratch'; use --task ft_all without --pretrained_path weights")
     if not torch.cuda.is_available():
         raise RuntimeError("generate_model needs a HIP device: cstp_amd has no CPU execution path")
-    if opts.model_name == "r3d_byol":        # models/model.py:65-70: R3DBYOL(pretrain=..., [cls_bn=True,] opts=opts)
-        if opts.task in PRETRAIN_TASKS:
-            model = R3DBYOL(pretrain=True, opts=opts)
-        else:
-            model = R3DBYOL(pretrain=False, cls_bn=True, opts=opts)
-    elif opts.model_name == "i3d_byol":      # models/model.py:66-71: I3DBYOL(pretrain=..., opts=opts)
-        model = I3DBYOL(pretrain=opts.task in PRETRAIN_TASKS, opts=opts)
-    elif opts.model_name == "s3d_byol":      # models/model.py:54-59: S3DGBYOL(pretrain=..., gating=True, slow=False, ...)
-        act = getattr(opts, "act_dtype", "fp32") or "fp32"
-        model = S3DGBYOL(pretrain=opts.task in PRETRAIN_TASKS, gating=True, slow=False, num_classes=opts.n_classes,
-                         act_dtype=act)
-    else:
-        act = getattr(opts, "act_dtype", "fp32") or "fp32"
-        layer_sizes = layer_sizes_for_depth(opts.model_depth)
-        if opts.task in PRETRAIN_TASKS:
-            model = R21DBYOL(pretrain=True, layer_sizes=layer_sizes, act_dtype=act)
-        else:
-            model = R21DBYOL(pretrain=False, num_classes=opts.n_classes, cls_bn=True, layer_sizes=layer_sizes, act_dtype=act)
+    if opts.task in RETRIEVAL_TASKS:
+        return _retrieval_model(opts)
+    model = _build(opts, opts.task in PRETRAIN_TASKS)
     local_rank = opts.local_rank if getattr(opts, "local_rank", -1) not in (-1, None) else 0
     torch.cuda.set_device(local_rank)
     model.cuda(local_rank)

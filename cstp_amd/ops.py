@@ -1724,6 +1724,40 @@ def ntxent(reps, temperature):
     return _NTXent.apply(reps, float(temperature))
 
 
+SIM_TOPK_MAX_K = 64
+
+
+def sim_topk(q, g, k, exclude_self=False):
+    """The k most similar rows of g [ng, d] for every row of q [nq, d] (dot products; L2-normalise both first for cosine):
+    -> (val [nq, k] fp32, idx [nq, k] int32), by similarity descending, the lower gallery row first where two similarities are
+    bit-equal, (-inf, -1) where candidates run out.  ``exclude_self``: q and g are the same set, row i skips candidate i.
+    The [nq, ng] matrix never exists (csrc/retrieve.hip); scratch grows with nq * k.  No autograd."""
+    if q.dim() != 2 or g.dim() != 2:
+        raise _lib.CstpError("sim_topk expects [rows, features] tensors, got %s and %s" % (tuple(q.shape), tuple(g.shape)))
+    if q.shape[1] != g.shape[1]:
+        raise _lib.CstpError("sim_topk: queries have %d features, the gallery %d" % (q.shape[1], g.shape[1]))
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= SIM_TOPK_MAX_K:
+        raise _lib.CstpError("sim_topk: k must be an int in 1..%d, got %r" % (SIM_TOPK_MAX_K, k))
+    for t, name in ((q, "sim_topk queries"), (g, "sim_topk gallery")):      # the dtype first: _req asks for the device first
+        if t.dtype != torch.float32:
+            raise _lib.CstpError("%s must be float32, got %s" % (name, t.dtype))
+    q, g = _req(q.detach(), "sim_topk queries"), _req(g.detach(), "sim_topk gallery")
+    lib = _lib.load()
+    if q.device != g.device:
+        raise _lib.CstpError("sim_topk: queries on %s, gallery on %s" % (q.device, g.device))
+    nq, d = q.shape
+    ng = g.shape[0]
+    if nq < 1 or ng < 1 or d < 1:
+        raise _lib.CstpError("sim_topk: empty operand %s x %s" % (tuple(q.shape), tuple(g.shape)))
+    nbytes = lib.cstp_simtopk_workspace_bytes(nq, ng, d, k)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=q.device)      # private and exact: not the geometric arena
+    val = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+    idx = torch.empty((nq, k), dtype=torch.int32, device=q.device)
+    check(lib.cstp_simtopk(_stream(), q.data_ptr(), g.data_ptr(), nq, ng, d, k, 1 if exclude_self else 0, val.data_ptr(),
+                           idx.data_ptr(), ws.data_ptr(), ws.numel()), "cstp_simtopk")
+    return val, idx
+
+
 # ----------------------------------------------------------------------------------------------
 # flat-arena utilities (no autograd)
 # ----------------------------------------------------------------------------------------------

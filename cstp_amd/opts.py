@@ -10,6 +10,8 @@ Additions (all optional, defaults reproduce the reference):
   --bucket_cap_mb   DDP gradient bucket size (xGMI ring all-reduce is per-link bound)
   --act_dtype       fp32 (default) | bf16: storage type of the 5-D activations and their gradients (BASELINE configs[4]:
                     3D-ResNet-50, bf16; both backbones -- cstp_amd/r3d_byol.py, cstp_amd/r21d_byol.py)
+  --retrieval_k     the k of R@k for the retrieval driver (retrieval.py), each in 1..64 (default 1 5 10 20 50)
+  --retrieval_gallery_len   gallery videos of --dataset synthetic_video in the retrieval driver (queries: --synthetic_len / 4)
 torchrun passes LOCAL_RANK through the environment instead of --local_rank; both are honoured.
 """
 from __future__ import annotations
@@ -95,7 +97,16 @@ _FLAGS = [
     ("max_steps", 0, int, "stop each epoch after this many iterations (0 = all)"),
     ("bucket_cap_mb", 25, int, "DDP gradient bucket size in MB"),
     ("act_dtype", "fp32", str, "fp32 | bf16: activation storage type (r21d_byol and r3d_byol; s3d_byol and i3d_byol are fp32 only)"),
+    ("retrieval_gallery_len", 64, int, "retrieval.py with --dataset synthetic_video: number of gallery videos"),
 ]
+RETRIEVAL_MAX_K = 64      # ops.SIM_TOPK_MAX_K: one lane per list slot
+
+
+def _retrieval_k(text):
+    k = int(text)
+    if not 1 <= k <= RETRIEVAL_MAX_K:
+        raise argparse.ArgumentTypeError("--retrieval_k takes values in 1..%d, got %d" % (RETRIEVAL_MAX_K, k))
+    return k
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -109,6 +120,8 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--highest_val", default={"name": 0}, type=dict, help="best validation score store")
     parser.add_argument("--loss_weight", default=1.0, nargs="+", type=float,
                         help="weights of (byol, spatial overlap, temporal overlap, playback rate, rotation)")
+    parser.add_argument("--retrieval_k", default=[1, 5, 10, 20, 50], nargs="+", type=_retrieval_k,
+                        help="retrieval.py: the k of R@k, each in 1..%d" % RETRIEVAL_MAX_K)
     return parser
 
 

@@ -576,6 +576,14 @@ class ByolBase(nn.Module):
         (feature, projection), one without returns the feature alone."""
         return out[1] if isinstance(out, tuple) else out
 
+    def encode(self, x):
+        """The pooled backbone feature [B, d] (fp32) of a clip batch: the tensor the pretext heads (pb_cls) read in
+        ``_two_view_step``, for every pre-training wrapper, and the one the R(2+1)D / R3D / S3D-G fine-tune heads normalise (an
+        I3D fine-tune encoder ends in its classifier).  ``act_bf16`` rounds the clips to bf16 as the training step does.
+        Retrieval (cstp_amd.retrieval) calls it under model.eval() and torch.no_grad()."""
+        out = self.online_net(ops.to_bf16(x) if self.act_bf16 else x)
+        return out[0] if isinstance(out, tuple) else out
+
     def _head(self, head, x):
         """A two-view pretext head: the _MLP heads hold a BatchNorm and take the views as two groups, plain Linear heads do not."""
         return head(x, groups=2) if isinstance(head, _MLP) else head(x)

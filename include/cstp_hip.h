@@ -1,6 +1,7 @@
 /*
  * cstp_hip.h -- C ABI of libcstp_hip.so: the MI355X (gfx950) kernels behind the CSTP
- * R(2+1)D-BYOL pre-training step.
+ * BYOL pre-training step (R(2+1)D, 3D-ResNet, S3D-G and I3D backbones), its fine-tune / test callers, the GPU clip
+ * pipeline in front of it and the nearest-neighbour retrieval evaluation behind it.
  *
  * The reference (KT27-A/CSTP) owns no native code and no FFI: every op below is an ATen
  * call-site of its Python hot path, cited per entry point (paths relative to the
@@ -572,6 +573,25 @@ int cstp_bnrelu_concat_eval(void* stream, const cstp_bnc_branch* branches, int32
 int cstp_bnrelu_concat_backward(void* stream, const cstp_bnc_branch* branches, int32_t nbranch, int32_t n, int32_t s,
                                 int32_t groups, const float* dy, const float* save_mean, const float* save_invstd,
                                 const float* scale_shift, void* ws, size_t ws_bytes, int32_t accumulate);
+
+/* ---- nearest-neighbour video retrieval: streaming similarity top-k (csrc/retrieve.hip) -------------------------------------
+ * The evaluation protocol after the feature (no call-site in the reference): q [nq][d] queries, g [ng][d] gallery rows, fp32,
+ * row-major, FINITE (NaN handling is not specified), L2-normalised by the caller with cstp_l2_normalize_forward.
+ *   sim(i, j) = sum_c q[i][c] * g[j][c]     fp32 products, fp32 accumulation, c ascending (one fmaf chain per pair)
+ * val / idx [nq][k]: row i holds the k largest sim(i, .) and their gallery rows, by similarity descending; where two
+ * similarities are bit-equal the LOWER gallery index comes first.  Where fewer than k candidates exist (ng < k, or ng - 1 < k
+ * with exclude_self) the tail is idx = -1, val = -inf.  exclude_self != 0 (q and g are the same set): candidate j == i is skipped.
+ * Limits: 1 <= k <= 64, d >= 1, 1 <= nq, ng < 2^31 - 128; anything else is refused before any HIP call.
+ * The [nq][ng] matrix never exists: a block owns 64 queries and streams its share of the gallery in tiles of 128 rows, keeping k
+ * candidates per query.  With few queries the gallery is split over nsplit <= 32 blocks per query tile, whose lists go through
+ * the workspace and a second launch that merges them; the answer does not depend on nsplit.  Workspace:
+ * nsplit * nq * k * 8 bytes rounded up to 512, plus 256 -- at most 32 * nq * k * 8 + 768, growing with nq * k and never with
+ * nq * ng.  No atomics: two calls give the same bits.  One launch, two when the gallery is split.  The environment variable
+ * CSTP_SIMTOPK_NSPLIT (1..32, read by every call and by the workspace query) overrides nsplit: a developer knob, the tests pin
+ * the unsplit path with it. */
+size_t cstp_simtopk_workspace_bytes(int32_t nq, int32_t ng, int32_t d, int32_t k);
+int cstp_simtopk(void* stream, const float* q, const float* g, int32_t nq, int32_t ng, int32_t d, int32_t k,
+                 int32_t exclude_self, float* val, int32_t* idx, void* ws, size_t ws_bytes);
 
 #ifdef __cplusplus
 }
