@@ -462,7 +462,8 @@ def _direct(p) -> bool:
 
 OVERLAP_WGRAD = os.environ.get("CSTP_OVERLAP_WGRAD", "1") == "1"
 _side_streams = {}
-_join_pending = set()
+_join_pending = set()      # devices whose side stream the running backward pass used and has not joined yet ...
+_join_pass = -1            # ... and that pass (torch._C._current_graph_task_id)
 
 
 def _side_stream(device: torch.device) -> torch.cuda.Stream:
@@ -480,7 +481,17 @@ def _join_side_streams() -> None:
     _join_pending.clear()
 
 
+def _pending_side_joins():
+    """The device indices whose side stream still awaits its join (tests)."""
+    return sorted(_join_pending)
+
+
 def _queue_join(device: torch.device) -> None:
+    global _join_pass
+    task = torch._C._current_graph_task_id()
+    if task != _join_pass:       # another pass filled the set and raised before its callback ran: that pass is gone, queue anew
+        _join_pending.clear()
+        _join_pass = task
     if device.index not in _join_pending:
         if not _join_pending:
             torch.autograd.Variable._execution_engine.queue_callback(_join_side_streams)
@@ -522,7 +533,8 @@ def _place_wgrad(param, w, need, side_ok, wgrad, reads):
 # a one-element device tensor as a by-product and hangs it on the tensor it produced; the convolution that consumes that very
 # tensor object hands it to the 2xf16-split kernels, which otherwise spend one extra read of the tensor on measuring it.  The
 # attribute travels with the Python object only: any op in between (reshape, cat, add, an in-place update -- _version is
-# checked) drops it, and the kernels measure for themselves.
+# checked) drops it, and the kernels measure for themselves.  Only the public wrapper sees the tensor object apply() returns, so
+# forward hands it the cell in the call's own record (_Call): nothing a call sets up outlives the call.
 FUSE_ABSMAX = os.environ.get("CSTP_FUSE_ABSMAX", "1") != "0"
 # BatchNorm statistics as a by-product of the producing convolution (patch-kernel layers): 0 keeps the separate pass
 FUSE_BN_STATS = os.environ.get("CSTP_FUSE_BN_STATS", "1") != "0"
@@ -547,6 +559,16 @@ def _new_cell(like: torch.Tensor) -> Optional[torch.Tensor]:
     return torch.empty(1, dtype=torch.int32, device=like.device) if FUSE_ABSMAX else None
 
 
+class _Call:
+    """The side data of ONE op call.  The public wrapper makes it and hands it to ``apply()`` as a plain argument: ``pre`` is what
+    the wrapper found with _bnstats_of (a list per branch for bn_relu_concat); ``forward`` fills ``cell`` (the absmax cell the
+    wrapper hangs on the result) and ``stats`` (what _launch_forward returned).  It dies with the call, whether that raises or not."""
+    __slots__ = ("pre", "cell", "stats")
+
+    def __init__(self, pre=None):
+        self.pre, self.cell, self.stats = pre, None, None
+
+
 class GradJoin:
     """The gradients of ONE tensor that feeds ``n`` of these ops (the residual connection, r21d_byol.py:141-148: a block's
     input goes into conv1 AND into the addition behind bn2; in a downsample block into conv1 and the shortcut convolution)
@@ -554,8 +576,6 @@ class GradJoin:
     puts its gradient into the join's buffer (the first one creates it, convolutions after that ADD into it in their
     epilogue: cstp_conv3d_backward_data_acc) and hands autograd None; the last one adds its own and returns the sum.
     A fresh object per forward call; backward order is whatever the autograd engine chooses."""
-
-    _open = []                # joins that hold a partial sum (checked when the backward pass ends)
 
     def __init__(self, n: int):
         self.n, self.count, self.buf = int(n), 0, None
@@ -574,23 +594,19 @@ class GradJoin:
             if self.buf is None:
                 # first contributor: if the others never run (a consumer's input gradient pruned by autograd.grad(inputs=...),
                 # needs_input_grad False on one branch) the partial sum would silently vanish -- an end-of-backward check raises
-                GradJoin._open.append(self)
-                if len(GradJoin._open) == 1:
-                    torch.autograd.Variable._execution_engine.queue_callback(GradJoin._check_closed)
+                torch.autograd.Variable._execution_engine.queue_callback(self._close)
             self.buf = out
             return None
-        if self in GradJoin._open:
-            GradJoin._open.remove(self)
         self.buf, self.count = None, 0
         return out
 
-    @staticmethod
-    def _check_closed():
-        left = [(j.count, j.n) for j in GradJoin._open]
-        GradJoin._open.clear()
-        if left:
-            raise RuntimeError("GradJoin: %d residual joins ended the backward pass with contributors missing %r -- a consumer's "
-                               "input gradient was pruned; the block input's gradient would have been dropped" % (len(left), left))
+    def _close(self):
+        """End of the backward pass this join's first contributor ran in: nothing of it outlives the pass."""
+        count, self.buf, self.count = self.count, None, 0
+        if 0 < count < self.n:
+            raise RuntimeError("GradJoin: residual joins ended the backward pass with contributors missing (%d of %d ran) -- a "
+                               "consumer's input gradient was pruned; the block input's gradient would have been dropped"
+                               % (count, self.n))
 
 
 def _tune(desc, mode, src, w, out, ws):
@@ -652,10 +668,8 @@ def _data_grad(desc, x, w, param, dy, cell, nbytes, launch, join=None):
 
 
 class _Conv3d(torch.autograd.Function):
-    _last_stats = None
-
     @staticmethod
-    def forward(ctx, x, w, bias, stride, padding, bn_groups=0, bn_pivot=None, grad_join=None):
+    def forward(ctx, x, w, bias, stride, padding, bn_groups, bn_pivot, grad_join, call):
         lib = _lib.load()
         xam = _absmax_of(x)
         w_in = w
@@ -668,7 +682,7 @@ class _Conv3d(torch.autograd.Function):
         b = None if bias is None else _req(bias, "conv3d bias")
         _tune(desc, 0, x, w, y, ws)
         with _span("conv3d_forward", lambda: _desc_key(desc)):
-            _Conv3d._last_stats = _packed_call(
+            call.stats = _packed_call(
                 _own_pack(w, w_in), "f", x.shape, x.device, nbytes,
                 lambda ws: _launch_forward(desc, x, w, b, None, y, ws, xam, bn_groups, bn_pivot), _dispatch_facts((x, y), xam))
         ctx.save_for_backward(x, w)
@@ -718,7 +732,7 @@ class _Conv3d(torch.autograd.Function):
             s = dy.numel() // (n * k)
             db = torch.empty(k, dtype=torch.float32, device=dy.device)
             check(lib.cstp_channel_sum(_stream(), dy.data_ptr(), db.data_ptr(), n, k, s, None, 0), "cstp_channel_sum")
-        return dx, dw, db, None, None, None, None, None
+        return dx, dw, db, None, None, None, None, None, None
 
 
 def conv3d(x, w, bias=None, stride=1, padding=0, bn_groups=0, bn_pivot=None, grad_join=None):
@@ -731,11 +745,10 @@ def conv3d(x, w, bias=None, stride=1, padding=0, bn_groups=0, bn_pivot=None, gra
         if bias is not None:
             raise _lib.CstpError("bf16-storage conv3d is bias-free (models/BE/r3d_byol.py:45-53)")
         return _Conv3dB16.apply(x, w, _triple(stride), _triple(padding), grad_join)
-    y = _Conv3d.apply(x, w, bias, _triple(stride), _triple(padding), int(bn_groups), bn_pivot, grad_join)
-    st = _Conv3d._last_stats
-    _Conv3d._last_stats = None
-    if st is not None:
-        y._cstp_bnstats = st + (y._version,)
+    call = _Call()
+    y = _Conv3d.apply(x, w, bias, _triple(stride), _triple(padding), int(bn_groups), bn_pivot, grad_join, call)
+    if call.stats is not None:
+        y._cstp_bnstats = call.stats + (y._version,)
     return y
 
 
@@ -750,7 +763,7 @@ def _bnstats_of(t, groups):
 def linear(x, w, bias=None):
     """F.linear drop-in for 2-D x: the 1x1x1 convolution over [B][F][1][1][1]."""
     y = _Conv3d.apply(x.reshape(x.shape[0], x.shape[1], 1, 1, 1), w.reshape(w.shape[0], w.shape[1], 1, 1, 1), bias,
-                      (1, 1, 1), (0, 0, 0), 0, None, None)
+                      (1, 1, 1), (0, 0, 0), 0, None, None, _Call())
     return y.reshape(x.shape[0], w.shape[0])
 
 
@@ -779,11 +792,8 @@ def _bn_param_grads(need_gamma, need_beta, pg, pb, gamma):
 
 
 class _BNAct(torch.autograd.Function):
-    _last_cell = None
-    _pre_stats = None     # (partial sums, nsplit) the producing convolution left for this call (batch_norm_act sets it)
-
     @staticmethod
-    def forward(ctx, x, gamma, beta, residual, running_mean, running_var, relu, eps, momentum, groups, grad_join=None):
+    def forward(ctx, x, gamma, beta, residual, running_mean, running_var, relu, eps, momentum, groups, grad_join, call):
         lib = _lib.load()
         x, res, n, c, s = _bn_operands(_req, x, residual, groups)
         gamma = _req(gamma, "batch_norm weight")
@@ -797,8 +807,7 @@ class _BNAct(torch.autograd.Function):
         remask = relu and res is None and s > 1
         ss = torch.empty(groups * c * 2, dtype=torch.float32, device=x.device) if remask else None
         cell = _new_cell(x) if s > 1 else None
-        pre = _BNAct._pre_stats
-        _BNAct._pre_stats = None
+        pre = call.pre           # (partial sums, nsplit, cell) the producing convolution left for this call, or None
         with _span("bn_forward", (n, c, s, groups, res is not None, bool(relu))):
             if pre is not None and s > 1:
                 check(lib.cstp_bn_forward_train_pre(_stream(), x.data_ptr(), _ptr(res), y.data_ptr(), gamma.data_ptr(),
@@ -811,7 +820,7 @@ class _BNAct(torch.autograd.Function):
                                                    beta.data_ptr(), _ptr(running_mean), _ptr(running_var), mean.data_ptr(),
                                                    invstd.data_ptr(), _ptr(ss), n, c, s, groups, eps, momentum, 1 if relu else 0,
                                                    ws.data_ptr(), ws.numel(), _ptr(cell)), "cstp_bn_forward_train")
-        _BNAct._last_cell = cell     # batch_norm_act hangs it on the tensor object apply() returns
+        call.cell = cell         # batch_norm_act hangs it on the tensor object apply() returns
         if remask:
             ctx.save_for_backward(x, ss, gamma, mean, invstd)
         else:
@@ -848,7 +857,7 @@ class _BNAct(torch.autograd.Function):
             dres = ctx.grad_join.contribute(lambda: dres, lambda buf: buf.add_(dres))
         if direct:
             dgamma = dbeta = None
-        return dx, dgamma, dbeta, dres, None, None, None, None, None, None, None
+        return dx, dgamma, dbeta, dres, None, None, None, None, None, None, None, None
 
 
 def batch_norm_act(x, gamma, beta, running_mean=None, running_var=None, residual=None, relu=False, eps=BN_EPS,
@@ -859,11 +868,10 @@ def batch_norm_act(x, gamma, beta, running_mean=None, running_var=None, residual
     if x.dtype == torch.bfloat16:
         return _BNActB16.apply(x, gamma, beta, residual, running_mean, running_var, bool(relu), float(eps), float(momentum),
                                int(groups), grad_join)
-    _BNAct._pre_stats = _bnstats_of(x, int(groups))
+    call = _Call(_bnstats_of(x, int(groups)))
     y = _BNAct.apply(x, gamma, beta, residual, running_mean, running_var, bool(relu), float(eps), float(momentum),
-                     int(groups), grad_join)
-    _tag_absmax(y, _BNAct._last_cell)
-    _BNAct._last_cell = None
+                     int(groups), grad_join, call)
+    _tag_absmax(y, call.cell)
     return y
 
 
@@ -904,15 +912,12 @@ class _BNReluConv3d(torch.autograd.Function):
     convolution applies x*scale+shift (+ReLU) inside its gather.  Backward: weight gradient with the same transform
     recomputed in ITS gather (side stream, straight into the gradient arena), data gradient of the convolution, then the
     BN backward with the ReLU mask recomputed from x."""
-    _pre_stats = None     # (partials, nsplit, cell) of the producing convolution (bn_relu_conv3d sets it)
-    _last_stats = None    # what THIS convolution left for the BatchNorm behind it (out_groups > 0), as _Conv3d._last_stats
 
     @staticmethod
     def forward(ctx, x, gamma, beta, running_mean, running_var, w, stride, padding, groups, relu, eps, momentum,
-                out_groups=0, out_pivot=None):
+                out_groups, out_pivot, call):
         lib = _lib.load()
-        pre = _BNReluConv3d._pre_stats
-        _BNReluConv3d._pre_stats = None
+        pre = call.pre           # (partials, nsplit, cell) of the producing convolution, or None
         w_in, g_in, b_in = w, gamma, beta
         x = _req(x, "bn_relu_conv3d input")
         gamma, beta, w = _req(gamma, "bn weight"), _req(beta, "bn bias"), _req(w, "conv weight")
@@ -944,7 +949,7 @@ class _BNReluConv3d(torch.autograd.Function):
         # sums and range beside y (the temporal patch kernel igemm_k1t<.., STATS, AFF>)
         with _span("conv3d_forward", lambda: _desc_key(desc)):
             # ("fa": a forward that carries the in_affine may run another kernel variant -- another pack -- than the plain one)
-            _BNReluConv3d._last_stats = _packed_call(
+            call.stats = _packed_call(       # (for the BatchNorm behind this convolution, as _Conv3d's)
                 _own_pack(w, w_in), "fa", x.shape, x.device, nbytes,
                 lambda ws: _launch_forward(desc, x, w, None, aff, y, ws, zam, out_groups, out_pivot), _dispatch_facts((x, y), zam))
         ctx.save_for_backward(x, gamma, mean, invstd, ss, w)
@@ -994,7 +999,7 @@ class _BNReluConv3d(torch.autograd.Function):
             _tag_absmax(dx, cell)
             if direct:
                 dgamma = dbeta = None
-        return dx, dgamma, dbeta, None, None, dw, None, None, None, None, None, None, None, None
+        return dx, dgamma, dbeta, None, None, dw, None, None, None, None, None, None, None, None, None
 
 
 def in_affine_fused(x_shape, w_shape, stride, padding, groups) -> bool:
@@ -1009,13 +1014,11 @@ def bn_relu_conv3d(x, gamma, beta, running_mean, running_var, w, stride=1, paddi
     """conv3d(act(batch_norm_train(x)), w) with the BN apply fused into the convolution's gather.  Where the convolution that
     produced ``x`` left the BatchNorm's sums and range beside it (conv3d(.., bn_groups=groups)) no pass reads x before the
     consuming convolution does.  ``bn_groups`` / ``bn_pivot``: as conv3d's -- the BatchNorm BEHIND this convolution."""
-    _BNReluConv3d._pre_stats = _bnstats_of(x, int(groups))
+    call = _Call(_bnstats_of(x, int(groups)))
     y = _BNReluConv3d.apply(x, gamma, beta, running_mean, running_var, w, _triple(stride), _triple(padding), int(groups),
-                            bool(relu), float(eps), float(momentum), int(bn_groups), bn_pivot)
-    st = _BNReluConv3d._last_stats
-    _BNReluConv3d._last_stats = None
-    if st is not None:
-        y._cstp_bnstats = st + (y._version,)
+                            bool(relu), float(eps), float(momentum), int(bn_groups), bn_pivot, call)
+    if call.stats is not None:
+        y._cstp_bnstats = call.stats + (y._version,)
     return y
 
 
@@ -1099,10 +1102,9 @@ def global_avg_pool(x):
 class _GateConcat(torch.autograd.Function):
     """y = cat_i(sigmoid(fc_i(mean_s x_i)) * x_i) over the branches of one SepInception block (s3dg.py:100-110, :150-163):
     two launches forward, three backward, for all branches together."""
-    _last_cell = None
 
     @staticmethod
-    def forward(ctx, nb, save, *args):
+    def forward(ctx, nb, save, call, *args):
         lib = _lib.load()
         xs = [_req(x, "gate_concat branch") for x in args[:nb]]
         ws = [_req(w, "gate_concat weight") for w in args[nb:2 * nb]]
@@ -1129,7 +1131,7 @@ class _GateConcat(torch.autograd.Function):
         with _span("gate_forward", (n, s, tuple(cs))):
             check(lib.cstp_gate_concat_forward(_stream(), br, nb, n, s, y.data_ptr(), m.data_ptr(), _ptr(g), _ptr(cell)),
                   "cstp_gate_concat_forward")
-        _GateConcat._last_cell = cell
+        call.cell = cell
         if save:
             ctx.save_for_backward(*xs, *ws, m, g)
             ctx.params = args[nb:3 * nb]       # the parameter objects themselves (.grad may be an arena slice)
@@ -1148,7 +1150,7 @@ class _GateConcat(torch.autograd.Function):
         dy = _req(dy, "gate_concat grad_output")
         dxs = [torch.empty_like(x) for x in xs]
         # gradients of leaf parameters whose .grad is a live slice of the flat arena are added there by the kernel (as the BN ops do)
-        direct = all(ctx.needs_input_grad[2 + nb:2 + 3 * nb]) and all(_direct(p) for p in ctx.params)
+        direct = all(ctx.needs_input_grad[3 + nb:3 + 3 * nb]) and all(_direct(p) for p in ctx.params)
         dws = [p.grad for p in ctx.params[:nb]] if direct else [torch.empty_like(w) for w in ws]
         dbs = [p.grad for p in ctx.params[nb:]] if direct else [torch.empty(c, dtype=torch.float32, device=dy.device) for c in cs]
         br = (_lib.GateBranch * nb)(*[_lib.GateBranch(x.data_ptr(), w.data_ptr(), b.data_ptr(), dx.data_ptr(), dw.data_ptr(),
@@ -1160,8 +1162,8 @@ class _GateConcat(torch.autograd.Function):
             check(lib.cstp_gate_concat_backward(_stream(), br, nb, n, s, dy.data_ptr(), m.data_ptr(), g.data_ptr(), wsp.data_ptr(),
                                                 wsp.numel(), 1 if direct else 0), "cstp_gate_concat_backward")
         if direct:
-            return (None, None, *dxs) + (None,) * (2 * nb)
-        return (None, None, *dxs, *dws, *dbs)
+            return (None, None, None, *dxs) + (None,) * (2 * nb)
+        return (None, None, None, *dxs, *dws, *dbs)
 
 
 def gate_concat(branches, gates):
@@ -1179,9 +1181,9 @@ def gate_concat(branches, gates):
         if t.dtype == torch.bfloat16:
             raise _lib.CstpError("gate_concat is fp32 only (S3D-G has no bf16-storage path)")
     save = torch.is_grad_enabled() and any(t.requires_grad for t in branches + ws + bs)
-    y = _GateConcat.apply(len(branches), save, *branches, *ws, *bs)
-    _tag_absmax(y, _GateConcat._last_cell)
-    _GateConcat._last_cell = None
+    call = _Call()
+    y = _GateConcat.apply(len(branches), save, call, *branches, *ws, *bs)
+    _tag_absmax(y, call.cell)
     return y
 
 
@@ -1288,11 +1290,9 @@ class _BNReluConcat(torch.autograd.Function):
     """y = cat_i(relu(batch_norm_train(x_i))) over the branches of one I3D Mixed block (i3d_byol.py:214-220): two launches
     forward (three when a branch brings no statistics), two backward, for all branches together.  Saved for backward, in this
     order: the nb inputs, the nb weights, save_mean and save_invstd [groups * C], the (scale, shift) table."""
-    _last_cell = None
-    _pre_stats = None      # per branch: what the producing convolution left (bn_relu_concat sets it)
 
     @staticmethod
-    def forward(ctx, nb, save, groups, eps, momentum, running, *args):
+    def forward(ctx, nb, save, groups, eps, momentum, running, call, *args):
         lib = _lib.load()
         xs = [_req(x, "bn_relu_concat branch") for x in args[:nb]]
         gammas = [_req(g, "bn_relu_concat weight") for g in args[nb:2 * nb]]
@@ -1311,8 +1311,7 @@ class _BNReluConcat(torch.autograd.Function):
         ctot = sum(cs)
         s = xs[0].numel() // (n * cs[0])
         dev = xs[0].device
-        pre = _BNReluConcat._pre_stats or [None] * nb
-        _BNReluConcat._pre_stats = None
+        pre = call.pre           # per branch: what the producing convolution left, or None
         y = torch.empty((n, ctot) + spatial, dtype=torch.float32, device=dev)
         mean = torch.empty(groups * ctot, dtype=torch.float32, device=dev)
         invstd = torch.empty(groups * ctot, dtype=torch.float32, device=dev)
@@ -1327,7 +1326,7 @@ class _BNReluConcat(torch.autograd.Function):
             check(lib.cstp_bnrelu_concat_forward(_stream(), br, nb, n, s, groups, eps, momentum, y.data_ptr(), mean.data_ptr(),
                                                  invstd.data_ptr(), ss.data_ptr(), wsp.data_ptr(), wsp.numel(), _ptr(cell)),
                   "cstp_bnrelu_concat_forward")
-        _BNReluConcat._last_cell = cell
+        call.cell = cell
         if save:
             ctx.save_for_backward(*xs, *gammas, mean, invstd, ss)
             ctx.params = args[nb:3 * nb]       # the parameter objects themselves (.grad may be an arena slice)
@@ -1347,7 +1346,7 @@ class _BNReluConcat(torch.autograd.Function):
         dy = _req(dy, "bn_relu_concat grad_output")
         dxs = [torch.empty_like(x) for x in xs]
         # gradients of leaf parameters whose .grad is a live slice of the flat arena are added there by the kernel (as _BNAct does)
-        direct = all(ctx.needs_input_grad[6 + nb:6 + 3 * nb]) and all(_direct(p) for p in ctx.params)
+        direct = all(ctx.needs_input_grad[7 + nb:7 + 3 * nb]) and all(_direct(p) for p in ctx.params)
         dgs = [p.grad for p in ctx.params[:nb]] if direct else [torch.empty_like(g) for g in gammas]
         dbs = [p.grad for p in ctx.params[nb:]] if direct else [torch.empty_like(g) for g in gammas]
         cells = torch.empty(nb, dtype=torch.int32, device=dy.device) if FUSE_ABSMAX else None
@@ -1363,7 +1362,7 @@ class _BNReluConcat(torch.autograd.Function):
         if cells is not None:
             for i, dx in enumerate(dxs):
                 _tag_absmax(dx, cells[i:i + 1])
-        head = (None,) * 6
+        head = (None,) * 7
         if direct:
             return head + tuple(dxs) + (None,) * (2 * nb)
         return head + tuple(dxs) + tuple(dgs) + tuple(dbs)
@@ -1392,10 +1391,9 @@ def bn_relu_concat(branches, bns, groups=1, eps=BN_EPS, momentum=BN_MOMENTUM):
     running = [(None if b[2] is None else _req(b[2], "running_mean"), None if b[3] is None else _req(b[3], "running_var"))
                for b in bns]
     save = torch.is_grad_enabled() and any(t.requires_grad for t in branches + gammas + betas)
-    _BNReluConcat._pre_stats = [_bnstats_of(x, int(groups)) for x in branches]
-    y = _BNReluConcat.apply(nb, save, int(groups), float(eps), float(momentum), running, *branches, *gammas, *betas)
-    _tag_absmax(y, _BNReluConcat._last_cell)
-    _BNReluConcat._last_cell = None
+    call = _Call([_bnstats_of(x, int(groups)) for x in branches])
+    y = _BNReluConcat.apply(nb, save, int(groups), float(eps), float(momentum), running, call, *branches, *gammas, *betas)
+    _tag_absmax(y, call.cell)
     return y
 
 

@@ -234,24 +234,24 @@ class PretrainStep:
         if self._flat_grad is not None:
             sync_buffers(self.model)                  # DDP's per-forward buffer broadcast (see the class docstring)
         sync_ctx = self.model.no_sync() if self._flat_grad is not None else contextlib.nullcontext()
-        if self._reducer is not None:
-            self._reducer.begin()
         plan = self._packs
-        if plan is not None:
-            ops.pack_plan = plan
-            plan.tick()
-            plan.armed = True
-            plan.replay("online")          # every online / predictor / head FORWARD weight pack of this step: one launch
-            self._pack_side = None
-            if plan.state == "replay" and "online_d" in plan.tables and clip_1.is_cuda:
-                # ... and their data-gradient packs beside the forward pass, on the weight-gradient side stream
-                main = torch.cuda.current_stream(clip_1.device)
-                side = ops._side_stream(clip_1.device)
-                side.wait_stream(main)     # (the optimizer step that wrote the weights ran on the main stream)
-                with torch.cuda.stream(side):
-                    plan.replay("online_d")
-                self._pack_side = side
-        try:
+        try:      # (whatever the step sets up from here on is undone below if it raises)
+            if self._reducer is not None:
+                self._reducer.begin()
+            if plan is not None:
+                ops.pack_plan = plan
+                plan.tick()
+                plan.armed = True
+                plan.replay("online")          # every online / predictor / head FORWARD weight pack of this step: one launch
+                self._pack_side = None
+                if plan.state == "replay" and "online_d" in plan.tables and clip_1.is_cuda:
+                    # ... and their data-gradient packs beside the forward pass, on the weight-gradient side stream
+                    main = torch.cuda.current_stream(clip_1.device)
+                    side = ops._side_stream(clip_1.device)
+                    side.wait_stream(main)     # (the optimizer step that wrote the weights ran on the main stream)
+                    with torch.cuda.stream(side):
+                        plan.replay("online_d")
+                    self._pack_side = side
             with sync_ctx:
                 out = self._forward_backward(clip_1, clip_2, spa, tem, pb, rot_1, rot_2)
         except BaseException:

@@ -161,3 +161,41 @@ def test_one_two_view_step_and_one_overlap_switch():
     for cls in (r21d_byol.R21DBYOL, r3d_byol.R3DBYOL, s3dg_byol.S3DGBYOL, i3d_byol.I3DBYOL):
         assert issubclass(cls, base) and "_two_view_step" not in vars(cls)
         assert cls._two_view_step is base._two_view_step
+
+
+def test_pretrain_step_cleans_up_when_the_pack_replay_fails(monkeypatch):
+    """Whatever PretrainStep.__call__ sets up before the forward pass -- the reducer begun, the pack plan armed -- is undone when
+    the top-of-step replay raises: nothing a step sets up outlives the step."""
+    from cstp_amd import ops
+    from cstp_amd.train import PretrainStep
+
+    class Model(torch.nn.Module):
+        def forward(self, x1, x2, o_type=None):
+            raise AssertionError("the step must not get as far as the forward pass")
+
+    class Optimizer:
+        def zero_grad(self): pass
+        def step(self): raise AssertionError("the step must not reach the optimizer")
+
+    class Reducer:
+        def __init__(self): self.log = []
+        def begin(self): self.log.append("begin")
+        def abort(self): self.log.append("abort")
+        def finish(self): self.log.append("finish")
+
+    def failing_replay(group):
+        assert plan.armed
+        raise RuntimeError("replay failed")
+
+    monkeypatch.setattr(ops, "pack_plan", None)          # (the step installs its plan there: restored afterwards)
+    step = PretrainStep(Model(), Optimizer(), [0.1, 1, 1, 1, 1], clip_grad_norm=False)
+    assert step._packs is None and step._reducer is None      # a CPU model without arenas gets neither: give it both
+    step._packs = plan = ops.PackPlan()
+    step._reducer = reducer = Reducer()
+    plan.state = "replay"
+    monkeypatch.setattr(plan, "replay", failing_replay)
+    z = torch.zeros(1)
+    with pytest.raises(RuntimeError, match="replay failed"):
+        step(z, z, z, z, z, z, z)
+    assert plan.armed is False and plan.state == "off"
+    assert reducer.log == ["begin", "abort"]
