@@ -411,7 +411,7 @@ conv_b16_kernel(const B16Conv g, const u16* __restrict__ src, const uint4* __res
     if (g.contig && sl == nullptr) {
       // bf16 results, 8 bytes per lane.  As the accumulator tile stands, lane = 16 * (position quad) + channel: the 16 lanes of a
       // store pass would write 16 pieces of 8 bytes, one per channel row.  The packed values travel to lane 4 * channel + quad
-      // first (two ds_bpermute per tile), so that a pass writes four runs of 32 contiguous bytes (igemm_k1p's KP_EPI_PERM).
+      // first (two ds_bpermute per tile), so that a pass writes four runs of 32 contiguous bytes (igemm_k1p's epilogue).
       const int sq = lane & 3, sfr = lane >> 2;
       const int perm_src = (16 * sq + sfr) * 4;
       const int Ps = n0 + wave * 32 + a * 16 + 4 * sq;

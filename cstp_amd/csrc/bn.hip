@@ -17,24 +17,14 @@
 
 namespace cstp {
 
-#ifndef CSTP_BN_NT
-#define CSTP_BN_NT 1       // streaming (non-temporal) vector stores / last-use loads in the apply kernels
-#endif
+// streaming (non-temporal) vector stores / last-use loads of the apply kernels
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void st4(float* p, const float4& v) {
-#if CSTP_BN_NT
   __builtin_nontemporal_store(f32x4v{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4v*>(p));
-#else
-  *reinterpret_cast<float4*>(p) = v;
-#endif
 }
 __device__ __forceinline__ float4 ld4_last(const float* p) {
-#if CSTP_BN_NT
   const f32x4v v = __builtin_nontemporal_load(reinterpret_cast<const f32x4v*>(p));
   return make_float4(v.x, v.y, v.z, v.w);
-#else
-  return *reinterpret_cast<const float4*>(p);
-#endif
 }
 
 

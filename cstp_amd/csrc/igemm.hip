@@ -23,26 +23,7 @@
 
 #include "common.h"
 
-#ifndef CSTP_PIN_PREFETCH
-#define CSTP_PIN_PREFETCH 0
-#endif
-#ifndef CSTP_SETPRIO
-#define CSTP_SETPRIO 0
-#endif
-#ifndef CSTP_NT_STORE
-#define CSTP_NT_STORE 1
-#endif
-#if CSTP_NT_STORE
 #define CSTP_STORE(ptr, val) __builtin_nontemporal_store((val), (ptr))
-#else
-#define CSTP_STORE(ptr, val) (*(ptr) = (val))
-#endif
-#ifndef CSTP_M16
-#define CSTP_M16 1          // 144-row tiles on the 16x16x4 MFMA for 129..144-channel layers
-#endif
-#ifndef CSTP_K2_BKN
-#define CSTP_K2_BKN 32      // positions per weight-gradient reduction tile (32 or 64)
-#endif
 
 namespace cstp {
 
@@ -814,7 +795,7 @@ static Tile pick_tile(int M, long npos, int nclass) {
         ((wm == 1 && mt <= 5) || (wm == 2 && mt <= 2) || (wm == 4 && mt == 1)))
       return Tile{mt, wm, 0, tpb == 2 ? 2 : 1};
   }
-  if (CSTP_M16 && M > 128 && M <= 144 && npos * nclass >= 1024) return Tile{9, 1, 1};   // exact 144-row tile
+  if (M > 128 && M <= 144 && npos * nclass >= 1024) return Tile{9, 1, 1};   // exact 144-row tile
   static const Tile cand[] = {{1, 1, 0}, {2, 1, 0}, {3, 1, 0}, {4, 1, 0}, {5, 1, 0}, {1, 2, 0}, {2, 2, 0}, {1, 4, 0}};
   Tile best = cand[0];
   double bestc = 1e300;
@@ -1628,7 +1609,7 @@ static Route route_dgrad(const cstp_conv_desc& d, const ConvPlan& p, const CallF
 static inline int wgrad_bm(const Tile& t) { return t.sp ? 16 * t.mt : (t.mt == 9 ? 144 : 32 * t.mt); }   // native 9 = nine 16-row tiles
 static Route route_wgrad(const cstp_conv_desc& d, const ConvPlan& p, const CallFacts& c) {
   const bool xform = c.xform_groups > 0;
-  const int native_mt = (CSTP_M16 && !p.straddle && d.k > 128 && d.k <= 144) ? 9 : pick_mt(d.k);
+  const int native_mt = (!p.straddle && d.k > 128 && d.k <= 144) ? 9 : pick_mt(d.k);
   Route r{};
   Tile& t = r.t;
   t = Tile{native_mt, 8, 0, 0, 0};   // 2048 blocks = ~8 per CU: measured 12 % faster than 4 per CU over the R18 layer set
@@ -1959,7 +1940,7 @@ extern "C" int cstp_conv3d_backward_weight_acc(void* stream, const cstp_conv_des
   const bool gather = r.t.sp != 0, stem = r.kern == Kern::GatherStem;
   const int mt = r.t.mt;
   const int npos = d.n * p.Do * p.Ho * p.Wo;
-  const int bkn = CSTP_K2_BKN;
+  constexpr int bkn = 32;                            // positions per weight-gradient reduction tile (igemm_k2's BKN: 32 or 64)
   const int kt_total = cdiv(npos, bkn);
   const int ntm = r.Mp / wgrad_bm(r.t), ntj = cdiv(p.w_Jtot, 128);
   int splits = cdiv(256 * r.t.wm, ntm * ntj);
@@ -2009,14 +1990,14 @@ extern "C" int cstp_conv3d_backward_weight_acc(void* stream, const cstp_conv_des
     const bool v4 = ((p.Do * p.Ho * p.Wo) % 4) == 0 && (reinterpret_cast<uintptr_t>(dy) & 15) == 0;
 #define CSTP_K2_ARGS mt, grid, s, g, dy, x, dwp, p.w_Jtot, p.w_Jp, kt_total, kt_per, ntm, ntj, splits, ia.ss, ia.npg, ia.groups, ia.relu, det_stride
     if (r.kern == Kern::NativeStraddle) {
-      if (v4) launch_k2<true, true, CSTP_K2_BKN, false>(CSTP_K2_ARGS);
-      else launch_k2<true, false, CSTP_K2_BKN, false>(CSTP_K2_ARGS);
+      if (v4) launch_k2<true, true, bkn, false>(CSTP_K2_ARGS);
+      else launch_k2<true, false, bkn, false>(CSTP_K2_ARGS);
     } else if (r.kern == Kern::NativeXform) {
-      if (v4) launch_k2<false, true, CSTP_K2_BKN, true>(CSTP_K2_ARGS);
-      else launch_k2<false, false, CSTP_K2_BKN, true>(CSTP_K2_ARGS);
+      if (v4) launch_k2<false, true, bkn, true>(CSTP_K2_ARGS);
+      else launch_k2<false, false, bkn, true>(CSTP_K2_ARGS);
     } else {
-      if (v4) launch_k2<false, true, CSTP_K2_BKN, false>(CSTP_K2_ARGS);
-      else launch_k2<false, false, CSTP_K2_BKN, false>(CSTP_K2_ARGS);
+      if (v4) launch_k2<false, true, bkn, false>(CSTP_K2_ARGS);
+      else launch_k2<false, false, bkn, false>(CSTP_K2_ARGS);
     }
 #undef CSTP_K2_ARGS
   }
@@ -2065,14 +2046,6 @@ extern "C" int cstp_conv3d_get_tile(const cstp_conv_desc* desc, int32_t mode, in
   tile4[3] = mode == 2 ? 0 : (t.tpb == 2 ? 2 : 1);
   return 0;
 }
-
-#if KP_DIAG & 16
-extern "C" int cstp_debug_stamps(unsigned long long* out8) {      // diagnostic builds only: read and reset the k1p stamps
-  unsigned long long zero[8] = {};
-  if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(cstp::kp_stamp), sizeof(zero)) != hipSuccess) return 1;
-  return hipMemcpyToSymbol(HIP_SYMBOL(cstp::kp_stamp), zero, sizeof(zero)) == hipSuccess ? 0 : 1;
-}
-#endif
 
 extern "C" int cstp_gemm_set_split_terms(int32_t terms) {
   CSTP_REQUIRE(terms >= 0 && terms <= 3, "split terms: 2 (f16 pair), 3 (bf16 triple), 1 (native f32 MFMA only) or 0 (environment default)");
@@ -2167,7 +2140,7 @@ extern "C" int cstp_conv3d_autotune(void* stream, const cstp_conv_desc* desc, in
     if (allow_split && !straddle && (wpatch_geom_ok(d) || twpatch_geom_ok(d))) cand[ncand++] = Tile{9, 1, 0, 0, 2};      // igemm_k2p / igemm_k2t
   } else {
     const bool stem = mode == 0 && straddle;
-    ncand = (CSTP_M16 && !stem && M > 128 && M <= 144) ? 9 : 8;
+    ncand = (!stem && M > 128 && M <= 144) ? 9 : 8;
     if (!stem) {       // the same tiles with two K-tiles per barrier
       const int n1 = ncand;
       for (int i = 0; i < n1; ++i) { cand[ncand] = cand[i]; cand[ncand].tpb = 2; ++ncand; }

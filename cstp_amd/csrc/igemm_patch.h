@@ -26,36 +26,12 @@
 
 #include <type_traits>
 
-#ifndef KP_RING6
-#define KP_RING6 0    // 1: six-slot weight ring at 64 rows (measured neutral: 58.19 vs 58.11 ms/step -- the weight DMA is not what the short K-tiles wait for)
-#endif
-#ifndef KP_GROUP3
-#define KP_GROUP3 0   // 1: 64-row tiles run THREE K-tiles (one filter row) per barrier through a six-slot weight ring -- a K-tile of 42 products
-#endif                // per wave lasts 672 matrix cycles.  MEASURED NEUTRAL (S1 data gradient 0.856 vs 0.834 ms, step 54.97 vs 54.92 ms same-box,
-                      // parity green): neither the barrier nor the weight-fragment wait is what the short K-tiles lose their time to
-#ifndef KP_EPI_PERM
-#define KP_EPI_PERM 1  // epilogue: lanes re-ordered (ds_bpermute) so that the four lanes of a channel are neighbours: a 16-lane
-#endif                 // group of a store then writes 4 runs of 64 bytes instead of 16 pieces of 16 bytes (one per channel row)
-#ifndef KP_XSPLIT
-#define KP_XSPLIT 4   // odd MT: column tiles of the shared last row tile that the FIRST row-wave pair takes (the second takes the rest)
-#endif
-#ifndef KP_DIAG
-#define KP_DIAG 0     // timing-only diagnostic builds (wrong results): bit 0 = no patch staging after the prologue, bit 1 = no weight
-#endif                // DMA after the prologue, bit 2 = no products, bit 3 = no output stores
-
 namespace cstp {
-
-#if KP_DIAG & 16
-// in-kernel stamps of consumer wave 0 of block 0 (diagnostic builds only): [0] cycles in K loops, [1] of them waiting at the
-// barrier, [2] from the top of a K-tile until its weight fragments have landed,
-// [3] epilogue cycles, [4] K-tiles, [5] items, [6] s_memrealtime ticks (100 MHz) over the K loops
-__device__ unsigned long long kp_stamp[8];
-#define KP_T() __builtin_amdgcn_s_memtime()
-#endif
 
 constexpr int KP_NPOS = 224;        // output positions per block
 constexpr int KP_NTW = 7;           // 16-column MFMA tiles per consumer wave (two wave columns)
 constexpr int KP_ROWS = 400;        // LDS rows (image positions incl. halo) per patch buffer: the host checks the geometry fits
+constexpr int KP_XSPLIT = 4;        // odd MT: column tiles of the shared last row tile that the FIRST row-wave pair takes (the second takes the rest)
 
 struct PGeom {
   int Cs;           // channels of the gathered tensor
@@ -158,17 +134,13 @@ igemm_k1p(const PGeom g, const uint4* __restrict__ wpk, const float* __restrict_
   constexpr int A_U4 = BM * 8;                       // uint4 per packed K-tile
   constexpr int A_DMA = BM / 8;                      // 1 KiB LDS-DMA pieces per K-tile
   constexpr int P_U4 = KP_ROWS * 8;
-  // Weight ring: three K-tiles where LDS is full (128 / 144 rows); SIX at 64 rows -- a K-tile of 42 products per consumer wave
-  // lasts ~0.3 us, and a weight piece requested two K-tiles ahead (0.6 us) is not back from L2 when its K-tile starts: the
-  // DMA waves' wait, and behind it the barrier, set the K-tile time.  Five K-tiles of lead cost 24 KB.
-  constexpr int GK = (KP_GROUP3 && MT == 4) ? 3 : 1;           // K-tiles per barrier
-  constexpr int RING = (GK == 3 || (KP_RING6 && MT == 4)) ? 6 : 3;
-  __shared__ uint4 smem[RING * A_U4 + 2 * P_U4 + 2 * (BM / 4) + (STATS ? BM + BM / 2 : 0)];
+  // Weight ring: three K-tiles, one K-tile per barrier.
+  __shared__ uint4 smem[3 * A_U4 + 2 * P_U4 + 2 * (BM / 4) + (STATS ? BM + BM / 2 : 0)];
   uint4* const ring = smem;
-  uint4* const patch = smem + RING * A_U4;
-  float* const inva_s = reinterpret_cast<float*>(smem + RING * A_U4 + 2 * P_U4);      // [2][BM], by item parity
-  double* const stat_s = reinterpret_cast<double*>(smem + RING * A_U4 + 2 * P_U4 + 2 * (BM / 4));   // STATS: [BM][2] sums of the block's group
-  unsigned* const mm_s = reinterpret_cast<unsigned*>(smem + RING * A_U4 + 2 * P_U4 + 2 * (BM / 4) + BM);   // STATS: [BM][2] range keys
+  uint4* const patch = smem + 3 * A_U4;
+  float* const inva_s = reinterpret_cast<float*>(smem + 3 * A_U4 + 2 * P_U4);      // [2][BM], by item parity
+  double* const stat_s = reinterpret_cast<double*>(smem + 3 * A_U4 + 2 * P_U4 + 2 * (BM / 4));   // STATS: [BM][2] sums of the block's group
+  unsigned* const mm_s = reinterpret_cast<unsigned*>(smem + 3 * A_U4 + 2 * P_U4 + 2 * (BM / 4) + BM);   // STATS: [BM][2] range keys
 
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -248,7 +220,7 @@ igemm_k1p(const PGeom g, const uint4* __restrict__ wpk, const float* __restrict_
       // count per iteration stays constant, which is what the counted wait relies on
       const unsigned so = (unsigned)((((size_t)d_mblk * nkt + d_kt) * A_U4) * 16);
       uint4* dst = ring + d_ring * A_U4;
-      d_ring = d_ring == RING - 1 ? 0 : d_ring + 1;
+      d_ring = d_ring == 2 ? 0 : d_ring + 1;
 #pragma unroll
       for (int pc = 0; pc < HALF_DMA; ++pc) {
         const int piece = dw_ * HALF_DMA + pc;
@@ -259,33 +231,17 @@ igemm_k1p(const PGeom g, const uint4* __restrict__ wpk, const float* __restrict_
         if (++d_kt == nkt) { d_kt = 0; ++d_it; item_of(d_it, tl_unused, d_mblk); }
       }
     };
-    if constexpr (GK == 3) {
-      // groups of three K-tiles: group g + 1 is requested into the three slots group g - 1 was read from and has the whole of
-      // group g's products (~1 us) to land; this wave has nothing else to do, so it simply waits for it
-      dma_next(); dma_next(); dma_next();
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      const int ngroups = nitems * nkt / 3;
-#pragma unroll 1
-      for (int gq = 0; gq < ngroups; ++gq) {
-        if (!(KP_DIAG & 2)) { dma_next(); dma_next(); dma_next(); }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-      }
-      return;
-    }
 #pragma unroll
-    for (int i = 0; i < RING - 1; ++i) dma_next();
+    for (int i = 0; i < 2; ++i) dma_next();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     const int total = nitems * nkt;
 #pragma unroll 1
     for (int k = 0; k < total; ++k) {
-      if (!(KP_DIAG & 2)) dma_next();                 // K-tile k + RING - 1 -> the slot K-tile k - 1 was read from
-      // (counted: everything but the youngest RING - 2 batches has landed = K-tile k + 1 is in LDS)
+      dma_next();                                     // K-tile k + 2 -> the slot K-tile k - 1 was read from
+      // (counted: everything but the youngest batch has landed = K-tile k + 1 is in LDS)
       if constexpr (HALF_DMA == 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
       else if constexpr (HALF_DMA == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else if constexpr (RING == 6) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
       __builtin_amdgcn_s_barrier();
     }
@@ -302,9 +258,6 @@ igemm_k1p(const PGeom g, const uint4* __restrict__ wpk, const float* __restrict_
     // rounds in flight with counted waits (igemm_split.h explains what a conditional load costs).
     constexpr int NR = (KP_ROWS + 63) / 64;            // 7
     static_assert(NR <= 7, "rounds must fit the nine taps of a channel block");
-#ifdef KP_SPRIO
-    __builtin_amdgcn_s_setprio(KP_SPRIO);
-#endif
     const int half = wave - 6;
     constexpr unsigned OOB = 0x80000000u;
     const __amdgpu_buffer_rsrc_t rs_src = make_rsrc(src, (unsigned)((size_t)(g.NF / g.D) * g.Cs * chs * 4));
@@ -343,9 +296,6 @@ igemm_k1p(const PGeom g, const uint4* __restrict__ wpk, const float* __restrict_
     const unsigned ch4 = (unsigned)(chs * 4);
     // channels past the tensor's last one (ragged last block) re-read the last channel: their packed weights are zero
     auto b_load = [&](unsigned vo, int cb, float (&v)[16]) __attribute__((always_inline)) {
-#if KP_DIAG & 64
-      { _Pragma("unroll") for (int j = 0; j < 16; ++j) v[j] = __builtin_bit_cast(float, vo + j); return; }   // no loads: split + store only
-#endif
       const int c0 = cb * 32 + half * 16;
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
@@ -355,9 +305,6 @@ igemm_k1p(const PGeom g, const uint4* __restrict__ wpk, const float* __restrict_
     };
     auto b_store = [&](int buf, int r, const float (&v)[16]) __attribute__((always_inline)) {
       const int l = lane + 64 * r;
-#if KP_DIAG & 32
-      { _Pragma("unroll") for (int j = 0; j < 16; ++j) asm volatile("" :: "v"(v[j])); return; }      // loads only: no split, no store
-#endif
       uint4 ph[2], pl[2];
       unsigned hh, ll;
 #define CSTP_SPLITH(J, DST, F) split2h(v[J], v[(J) + 1], sb, hh, ll); ph[DST].F = hh; pl[DST].F = ll;
@@ -462,10 +409,7 @@ igemm_k1p(const PGeom g, const uint4* __restrict__ wpk, const float* __restrict_
           prow[(4 + q_gch[r]) ^ x7] = pl;
         }
       };
-#ifndef KP_DEEP
-#define KP_DEEP 1
-#endif
-      if constexpr (KP_DEEP && MT != 4 && GK == 1 && !(KP_DIAG & 1)) {
+      if constexpr (MT != 4) {
         // ---- a whole channel block of lead (128 / 144 rows): channel block x + 2 (flat over the block's items) is REQUESTED
         // while block x is multiplied and STORED into the free patch buffer one block later, nine K-tiles after its loads
         // instead of four, at the first three taps of a block instead of taps 4..6.  Two register sets of three rounds (192
@@ -543,7 +487,7 @@ igemm_k1p(const PGeom g, const uint4* __restrict__ wpk, const float* __restrict_
         const bool next_item = it + 1 < nitems;
         for (int cb = 0; cb < g.ncb; ++cb) {
           const bool last_cb = cb + 1 == g.ncb;
-          const bool stage = (!last_cb || next_item) && !(KP_DIAG & 1);
+          const bool stage = !last_cb || next_item;
           if (last_cb && next_item) {
             item_of(it + 1, tile, mb_unused);
             quad_offsets(tile, qv_nxt);
@@ -554,10 +498,8 @@ igemm_k1p(const PGeom g, const uint4* __restrict__ wpk, const float* __restrict_
           for (int tap = 0; tap < 9; ++tap) {
             if (tap >= 4 && tap - 4 < QR) q_store(pb ^ 1, tap - 4, rq[tap - 4]);
             if (tap < QR) q_load(tap, stage ? (last_cb ? qv_nxt[tap] : qv_cur[tap]) : OOB, ncb_, rq[tap]);
-            if (GK == 1 || tap % 3 == 2) {
-              asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-              __builtin_amdgcn_s_barrier();
-            }
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
           }
           pb ^= 1;
         }
@@ -588,7 +530,7 @@ igemm_k1p(const PGeom g, const uint4* __restrict__ wpk, const float* __restrict_
       const bool next_item = it + 1 < nitems;
       for (int cb = 0; cb < g.ncb; ++cb) {
         const bool last_cb = cb + 1 == g.ncb;
-        const bool stage = (!last_cb || next_item) && !(KP_DIAG & 1);   // a next channel block (of this or the next item)
+        const bool stage = !last_cb || next_item;       // a next channel block (of this or the next item)
         if (last_cb && next_item) {
           item_of(it + 1, tile, mb_unused);
           patch_offsets(tile, voff_nxt);
@@ -612,10 +554,8 @@ igemm_k1p(const PGeom g, const uint4* __restrict__ wpk, const float* __restrict_
               b_load(vo, ncb_, rb[rl]);
             }
           }
-          if (GK == 1 || tap % 3 == 2) {
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-          }
+          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          __builtin_amdgcn_s_barrier();
         }
         pb ^= 1;
       }
@@ -643,10 +583,7 @@ igemm_k1p(const PGeom g, const uint4* __restrict__ wpk, const float* __restrict_
     for (int e = t; e < BM * 2; e += 256) { stat_s[e] = 0.0; mm_s[e] = (e & 1) ? 0u : 0xffffffffu; }   // (consumer threads are t < 256; read many barriers later)
   }
   __builtin_amdgcn_s_barrier();                        // the first item's prologue data is staged
-#ifndef KP_PRIO
-#define KP_PRIO 2
-#endif
-  if (KP_PRIO > 0) __builtin_amdgcn_s_setprio(KP_PRIO);    // the matrix stream outranks the staging waves it shares SIMDs with
+  __builtin_amdgcn_s_setprio(2);                       // the matrix stream outranks the staging waves it shares SIMDs with
 
   // two instantiations of the body (the shared row tile's column range is a compile-time constant) instead of branches
   auto body = [&](auto xj0_tag, auto xjn_tag) __attribute__((always_inline)) {
@@ -656,9 +593,6 @@ igemm_k1p(const PGeom g, const uint4* __restrict__ wpk, const float* __restrict_
   int pb = 0, slot3 = 0;
   for (int it = 0; it < nitems; ++it) {
     int tile, mblk;
-#if KP_DIAG & 16
-    const unsigned long long t_item0 = KP_T();
-#endif
     item_of(it, tile, mblk);
     const int pos0 = tile * KP_NPOS;
     // (pos0 is uniform: these three divisions are the item's only ones -- every per-lane position below is reached from
@@ -680,15 +614,6 @@ igemm_k1p(const PGeom g, const uint4* __restrict__ wpk, const float* __restrict_
     for (int j = 0; j < (XJN > 0 ? XJN : 1); ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r) accx[j][r] = 0.f;
-#if KP_DIAG & 128
-    // timing-only diagnostic (wrong results): the whole row tiles' products as v_mfma_f32_32x32x16_f16 -- the same multiply-add
-    // count in half the instructions, each holding the SIMD's issue port 8 of 32 cycles instead of 8 of 16
-    f32x16 accq[KP_NTW];
-#pragma unroll
-    for (int j = 0; j < KP_NTW; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) accq[j][r] = 0.f;
-#endif
 
     // LDS row of my column in each of my 7 column tiles, one line above / one column left of it; a tap adds dh * PITCH + dw
     int base[KP_NTW];
@@ -741,16 +666,8 @@ igemm_k1p(const PGeom g, const uint4* __restrict__ wpk, const float* __restrict_
     // one K-tile per call, NOT unrolled over the taps: with the tap a compile-time constant the compiler hoists all
     // 9 x 7 x 2 fragment addresses out of the loop (126 VGPRs) and spills the accumulators
     int tap = 0, dh_pitch = 0, dw = 0;                 // (slot3, the ring slot of the next K-tile, runs on across the items)
-#if KP_DIAG & 16
-    const bool stamp = blockIdx.x == 0 && wave == 0;
-    unsigned long long s_loop = 0, s_bar = 0, s_a = 0;
-    const unsigned long long t_loop0 = KP_T(), r_loop0 = __builtin_amdgcn_s_memrealtime();
-#endif
     auto ktile = [&](auto ph_tag) __attribute__((always_inline)) {
       constexpr int PH = decltype(ph_tag)::value;        // buffer of this K-tile's column tile 0
-#if KP_DIAG & 16
-      const unsigned long long t_top = KP_T();
-#endif
       const uint4* Ab = ring + slot3 * A_U4;
       const unsigned Bp = patch_lds + pb * (P_U4 * 16);
       const int ts = dh_pitch + dw;
@@ -771,51 +688,20 @@ igemm_k1p(const PGeom g, const uint4* __restrict__ wpk, const float* __restrict_
         ah[NI] = __builtin_bit_cast(f16x8, Ab[((MT - 1) * 16 + fr) * 8 + qa0]);
         al[NI] = __builtin_bit_cast(f16x8, Ab[((MT - 1) * 16 + fr) * 8 + qa1]);
       }
-#if KP_DIAG & 16
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      s_a += KP_T() - t_top;
-#endif
 #pragma unroll
       for (int j = 0; j < KP_NTW; ++j) {
         // column tile j + 2 (past the last: tiles 0, 1 of the next K-tile; past the item's last K-tile harmless reads,
         // issued again at the top of the next item) is requested now; tile j + 3's address is computed among tile j's products
-        // GK == 3: the staging waves write the NEXT channel block's patch until the barrier behind this block's last K-tile
-        // (tap 8), so its first two column tiles are NOT requested ahead of that barrier (the K loop requests them behind it)
-        const bool hold = GK == 3 && PH == 2 && j + 2 >= KP_NTW && tap == 8;
-        if (!hold) issue_b(bh[(PH + j + 2) % 3], bl[(PH + j + 2) % 3], addr_n);
+        issue_b(bh[(PH + j + 2) % 3], bl[(PH + j + 2) % 3], addr_n);
         if (j + 3 < KP_NTW) addr_n = b_addr(j + 3, Bp, ts);
         else addr_n = b_addr(j + 3 - KP_NTW, Bn, nts);
         // tile j (requested two groups ago) has landed once at most the four youngest reads are outstanding
-        if (!hold) asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
-        else if (j == KP_NTW - 2) asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory");
-        else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
         const f16x8 bhj = bh[(PH + j) % 3], blj = bl[(PH + j) % 3];
-#if KP_DIAG & 4
-        asm volatile("" :: "v"(bhj), "v"(blj));
-        if (j == 0) { _Pragma("unroll") for (int i = 0; i < NI + XA; ++i) asm volatile("" :: "v"(ah[i]), "v"(al[i])); }
-        continue;
-#endif
         // (j is a constant after unrolling: this test folds)
         const bool xj = XJN > 0 && j >= XJ0 && j < XJ0 + XJN;
         const int jx = xj ? j - XJ0 : 0;
-#if KP_DIAG & 128
-        if constexpr (NI == 4) {
-#pragma unroll
-          for (int i = 0; i < NI; i += 2) {
-            accq[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bhj, al[i], accq[j], 0, 0, 0);
-            accq[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(blj, ah[i + 1], accq[j], 0, 0, 0);
-            accq[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bhj, ah[i], accq[j], 0, 0, 0);
-          }
-          if (xj) {
-            accx[jx] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bhj, al[NI + XA - 1], accx[jx], 0, 0, 0);
-            accx[jx] = __builtin_amdgcn_mfma_f32_16x16x32_f16(blj, ah[NI + XA - 1], accx[jx], 0, 0, 0);
-            accx[jx] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bhj, ah[NI + XA - 1], accx[jx], 0, 0, 0);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-          continue;
-        }
-#endif
 #pragma unroll
         for (int i = 0; i < NI; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bhj, al[i], acc[i][j], 0, 0, 0);
         if (xj) accx[jx] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bhj, al[NI + XA - 1], accx[jx], 0, 0, 0);
@@ -828,50 +714,22 @@ igemm_k1p(const PGeom g, const uint4* __restrict__ wpk, const float* __restrict_
         // nothing moves across this point: the next group's issue stays behind these products
         __builtin_amdgcn_sched_barrier(0);
       }
-      slot3 = slot3 == RING - 1 ? 0 : slot3 + 1;
+      slot3 = slot3 == 2 ? 0 : slot3 + 1;
       tap = ntap; dw = ndw; dh_pitch = ndh; pb = npb;
-#if KP_DIAG & 16
-      const unsigned long long t_b0 = KP_T();
-#endif
       // (no drain in front of the barrier: every read of this K-tile's ring slot and of this channel block's patch buffer has
       // been waited for above; the two tiles in flight belong to the next K-tile and stay in flight across the barrier)
-      if (GK == 1 || PH == 2) __builtin_amdgcn_s_barrier();
-#if KP_DIAG & 16
-      s_bar += KP_T() - t_b0;
-#endif
+      __builtin_amdgcn_s_barrier();
     };
 #pragma unroll 1
     for (int kt = 0; kt < nkt; kt += 3) {
       ktile(std::integral_constant<int, 0>{});
       ktile(std::integral_constant<int, 1>{});
       ktile(std::integral_constant<int, 2>{});
-      if constexpr (GK == 3) {
-        if (tap == 0 && kt + 3 < nkt) {               // a new channel block of this item: its patch is complete behind the barrier
-          const unsigned Bq = patch_lds + pb * (P_U4 * 16);
-          issue_b(bh[0], bl[0], b_addr(0, Bq, 0));
-          issue_b(bh[1], bl[1], b_addr(1, Bq, 0));
-          addr_n = b_addr(2, Bq, 0);
-        }
-      }
     }
     // the next item's prologue re-issues into buffers 0 and 1: the two reads still in flight must have landed before that
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-#if KP_DIAG & 16
-    const unsigned long long t_loop1 = KP_T(), r_loop1 = __builtin_amdgcn_s_memrealtime();
-    s_loop = t_loop1 - t_loop0;
-#endif
     // (pb has moved on to the buffer that holds the next item's first channel block)
-#if KP_DIAG & 128
-    if constexpr (NI == 4) {
-#pragma unroll
-      for (int j = 0; j < KP_NTW; ++j)
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc[i][j][r] = accq[j][4 * i + r];
-    }
-#endif
 
     // ---- epilogue.  The products are issued with the POSITIONS as the MFMA's row operand and the weight rows as its column
     // operand, so the accumulator tile is the transpose of the usual one: col = lane & 15 is an OUTPUT ROW (channel) and
@@ -897,10 +755,10 @@ igemm_k1p(const PGeom g, const uint4* __restrict__ wpk, const float* __restrict_
     const bool vec_ok = (HW & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;     // uniform
     if (vec_ok) {
       // The accumulator tile has lane = 16 * (position quad q) + (channel fr): stored as it is, the 16 lanes of one pass of a
-      // 16-byte store hit 16 different channel rows.  KP_EPI_PERM: the values travel to lane 4 * fr + q first (ds_bpermute,
+      // 16-byte store hit 16 different channel rows.  So the values travel to lane 4 * fr + q first (ds_bpermute,
       // no memory), so that a pass writes four runs of 64 contiguous bytes; addresses follow the NEW lane's (channel, quad).
-      const int sq = KP_EPI_PERM ? (lane & 3) : q;                    // position quad / channel whose values I STORE
-      const int sfr = KP_EPI_PERM ? (lane >> 2) : fr;
+      const int sq = lane & 3;                                         // position quad / channel whose values I STORE
+      const int sfr = lane >> 2;
       const int perm_src = (16 * (lane & 3) + (lane >> 2)) * 4;        // byte index of the lane whose values I receive
       size_t obase[KP_NTW];
       bool nok[KP_NTW];
@@ -928,9 +786,7 @@ igemm_k1p(const PGeom g, const uint4* __restrict__ wpk, const float* __restrict_
 #pragma unroll
         for (int j = (i < NI ? 0 : XJ0); j < (i < NI ? KP_NTW : XJ0 + XJN); ++j) {
           const f32x4 v = i < NI ? acc[i < NI ? i : 0][j] : accx[i < NI ? 0 : j - XJ0];
-          if ((KP_DIAG & 8) && v[0] != 12345.f) continue;
           f32x4 vs = v * sc;
-#if KP_EPI_PERM
           {   // (the components through a plain struct: ext_vector component reads have miscompiled to component 0 here, see DESIGN)
             struct F4 { float a, b, c, d; };
             const F4 t4 = __builtin_bit_cast(F4, vs);
@@ -940,7 +796,6 @@ igemm_k1p(const PGeom g, const uint4* __restrict__ wpk, const float* __restrict_
             const float p3 = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(perm_src, __builtin_bit_cast(int, t4.d)));
             vs = f32x4{p0, p1, p2, p3};
           }
-#endif
           if (nok[j] && ms < g.M) {
             f32x4* dst = reinterpret_cast<f32x4*>(orow + obase[j]);
             *dst = g.acc ? *dst + vs : vs;
@@ -993,7 +848,6 @@ igemm_k1p(const PGeom g, const uint4* __restrict__ wpk, const float* __restrict_
           const f32x4 v = i < NI ? acc[i < NI ? i : 0][j] : accx[(i == NI && j >= XJ0 && j < XJ0 + XJN) ? j - XJ0 : 0];
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            if ((KP_DIAG & 8) && v[r] != 12345.f) continue;
             if (nk[r] && m < g.M) {
               float* dst = out + ob[r] + (size_t)m * chs;
               CSTP_STORE(dst, g.acc ? *dst + v[r] * sc : v[r] * sc);
@@ -1002,13 +856,6 @@ igemm_k1p(const PGeom g, const uint4* __restrict__ wpk, const float* __restrict_
         }
       }
     }
-#if KP_DIAG & 16
-    if (stamp && lane == 0) {
-      kp_stamp[0] += s_loop; kp_stamp[1] += s_bar; kp_stamp[2] += s_a; kp_stamp[3] += KP_T() - t_loop1;
-      kp_stamp[4] += (unsigned long long)nkt; kp_stamp[5] += 1; kp_stamp[6] += r_loop1 - r_loop0;
-      kp_stamp[7] += KP_T() - t_item0;              // the whole item: set-up + K loops + epilogue
-    }
-#endif
   }
   };
   using std::integral_constant;

@@ -23,10 +23,6 @@
 //   bank-conflict free;  consumer wave w owns columns 32w .. 32w+31 (two 16-column tiles) of all MT row tiles.
 #pragma once
 
-#ifndef CSTP_DIAG
-#define CSTP_DIAG 0      // diagnostic builds: 1 = consumers only synchronise (producer-bound time); 2 = producers only synchronise
-#endif
-
 namespace cstp {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -81,11 +77,7 @@ __device__ __forceinline__ void f16_scale(unsigned absmax_bits, float& scale, fl
 // f16 halves of h as their addend directly and write an f16 half of the result register (v_fma_mixlo/hi_f16: fp32 FMA, then
 // the conversion), where the generic form spends six (packed multiply, packed convert, two f16 -> f32 conversions, packed
 // subtract, packed convert) -- the split is most of the vector-ALU work of every gather / staging wave of the split kernels.
-#ifndef CSTP_SPLIT_MIX
-#define CSTP_SPLIT_MIX 1
-#endif
 __device__ __forceinline__ void split2h(float x0, float x1, float sc, unsigned& h, unsigned& l) {
-#if CSTP_SPLIT_MIX
   unsigned hh, ll;
   asm("v_fma_mixlo_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "=v"(hh) : "v"(x0), "v"(sc));
   asm("v_fma_mixhi_f16 %0, %1, %2, 0 op_sel:[0,0,0] op_sel_hi:[0,0,0]" : "+v"(hh) : "v"(x1), "v"(sc));
@@ -93,15 +85,6 @@ __device__ __forceinline__ void split2h(float x0, float x1, float sc, unsigned& 
   asm("v_fma_mixhi_f16 %0, %1, %2, -%3 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(ll) : "v"(x1), "v"(sc), "v"(hh));
   h = hh;
   l = ll;
-#else
-  f32x2 v = {x0, x1};
-  v = v * sc;
-  const f16x2 hh = __builtin_convertvector(v, f16x2);
-  const f32x2 r = v - __builtin_convertvector(hh, f32x2);
-  const f16x2 ll = __builtin_convertvector(r, f16x2);
-  h = __builtin_bit_cast(unsigned, hh);
-  l = __builtin_bit_cast(unsigned, ll);
-#endif
 }
 
 // largest magnitude of a tensor, as fp32 bits with the sign cleared (a NaN compares above everything and propagates)
@@ -619,11 +602,6 @@ igemm_k1s(const Geom g, const uint4* __restrict__ wps, const float* __restrict__
     // one younger tile (NLOADS loads) is outstanding when a set is consumed and emits counted waits; with a load under
     // `if` it must assume the younger loads may not exist and waits for everything, exposing the memory latency.
     int i = 0;
-#if CSTP_DIAG == 2
-    __syncthreads();
-    for (; i < ntiles; ++i) __syncthreads();
-    return;
-#endif
     if (ntiles >= 4) {
       issue_loads(ra0, rb0, as0);                     // tile 0
       issue_loads(ra1, rb1, as1);                     // tile 1
@@ -677,11 +655,6 @@ igemm_k1s(const Geom g, const uint4* __restrict__ wps, const float* __restrict__
       for (int r = 0; r < 4; ++r) acc[i][c][r] = 0.f;
 
   if (NP == 2 && t < BM) inva_s[t] = inv_a[m0 + t];  // rows < Mp: always readable; read back after the K loop's barriers
-#if CSTP_DIAG == 1
-  __syncthreads();
-  for (int i = 0; i < ntiles; ++i) __syncthreads();
-  if (ntiles >= 0) return;
-#endif
   __syncthreads();
   {
     int buf = 0;

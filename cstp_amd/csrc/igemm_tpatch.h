@@ -54,14 +54,13 @@ igemm_k1t(const TGeom g, const uint4* __restrict__ wpk, const float* __restrict_
   constexpr int A_U4 = BM * 8;                       // uint4 per packed K-tile
   constexpr int A_DMA = BM / 8;                      // 1 KiB LDS-DMA pieces per K-tile
   constexpr int P_U4 = KT_ROWS * 8;
-  constexpr int RING = KP_RING6 && MT == 4 ? 6 : 3;   // weight ring: six K-tiles at 64 rows (igemm_k1p explains)
-  __shared__ uint4 smem[RING * A_U4 + 2 * P_U4 + 2 * (BM / 4) + (STATS ? BM + BM / 2 : 0)];
+  __shared__ uint4 smem[3 * A_U4 + 2 * P_U4 + 2 * (BM / 4) + (STATS ? BM + BM / 2 : 0)];
   __shared__ __attribute__((aligned(16))) float aff_a[AFF ? 2 * KT_AFFC : 4], aff_b[AFF ? 2 * KT_AFFC : 4];
   uint4* const ring = smem;
-  uint4* const patch = smem + RING * A_U4;
-  float* const inva_s = reinterpret_cast<float*>(smem + RING * A_U4 + 2 * P_U4);      // [2][BM], by item parity
-  double* const stat_s = reinterpret_cast<double*>(smem + RING * A_U4 + 2 * P_U4 + 2 * (BM / 4));   // STATS: [BM][2] sums of the block's group
-  unsigned* const mm_s = reinterpret_cast<unsigned*>(smem + RING * A_U4 + 2 * P_U4 + 2 * (BM / 4) + BM);   // STATS: [BM][2] range keys
+  uint4* const patch = smem + 3 * A_U4;
+  float* const inva_s = reinterpret_cast<float*>(smem + 3 * A_U4 + 2 * P_U4);      // [2][BM], by item parity
+  double* const stat_s = reinterpret_cast<double*>(smem + 3 * A_U4 + 2 * P_U4 + 2 * (BM / 4));   // STATS: [BM][2] sums of the block's group
+  unsigned* const mm_s = reinterpret_cast<unsigned*>(smem + 3 * A_U4 + 2 * P_U4 + 2 * (BM / 4) + BM);   // STATS: [BM][2] range keys
 
   const int t = threadIdx.x, lane = t & 63;
   const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -146,24 +145,23 @@ igemm_k1t(const TGeom g, const uint4* __restrict__ wpk, const float* __restrict_
       for (int piece = 0; piece < A_DMA; ++piece)
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (__attribute__((address_space(3))) void*)(dst + piece * 64), 16,
                                                  (unsigned)(lane * 16 + piece * 1024), so, 0, 0);
-      d_ring = d_ring == RING - 1 ? 0 : d_ring + 1;   // (past the last item: the last K-tile again, into slots nobody reads)
+      d_ring = d_ring == 2 ? 0 : d_ring + 1;         // (past the last item: the last K-tile again, into slots nobody reads)
       if (d_it + 1 < nitems || d_kt + 1 < nkt) {
         if (++d_kt == nkt) { d_kt = 0; ++d_it; item_of(d_it, tl_unused, d_mblk); }
       }
     };
 #pragma unroll
-    for (int i = 0; i < RING - 1; ++i) dma_next();
+    for (int i = 0; i < 2; ++i) dma_next();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     const int total = nitems * nkt;
     static_assert(A_DMA == 8 || A_DMA == 16 || A_DMA == 18, "the counted wait below lists the piece counts");
 #pragma unroll 1
     for (int k = 0; k < total; ++k) {
-      dma_next();                                     // K-tile k + RING - 1 -> the slot K-tile k - 1 was read from
-      // (counted: everything but the youngest RING - 2 batches has landed = K-tile k + 1 is in LDS)
+      dma_next();                                     // K-tile k + 2 -> the slot K-tile k - 1 was read from
+      // (counted: everything but the youngest batch has landed = K-tile k + 1 is in LDS)
       if constexpr (A_DMA == 18) asm volatile("s_waitcnt vmcnt(18)" ::: "memory");
       else if constexpr (A_DMA == 16) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-      else if constexpr (RING == 6) asm volatile("s_waitcnt vmcnt(32)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
       __builtin_amdgcn_s_barrier();
     }
@@ -416,7 +414,7 @@ igemm_k1t(const TGeom g, const uint4* __restrict__ wpk, const float* __restrict_
         if (xj) accx[jx] = __builtin_amdgcn_mfma_f32_16x16x32_f16(bhj, ah[NI + XA - 1], accx[jx], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
       }
-      slot3 = slot3 == RING - 1 ? 0 : slot3 + 1;
+      slot3 = slot3 == 2 ? 0 : slot3 + 1;
       tap = ntap; pb = npb;
       __builtin_amdgcn_s_barrier();
     };
@@ -431,8 +429,8 @@ igemm_k1t(const TGeom g, const uint4* __restrict__ wpk, const float* __restrict_
 
     // ---- epilogue (igemm_k1p's: transposed tile, one 16-byte store per lane and column tile).  A lane's four positions
     // p0 .. p0 + 3 are columns j0 .. j0 + 3 of frame d0 + p0 / 28 (28 is a multiple of four: never across frames).
-    // (KP_EPI_PERM, as in igemm_k1p: the values travel to lane 4 * channel + quad before they are stored)
-    const int sq = KP_EPI_PERM ? (lane & 3) : q, sfr = KP_EPI_PERM ? (lane >> 2) : fr;
+    // (as in igemm_k1p: the values travel to lane 4 * channel + quad before they are stored)
+    const int sq = lane & 3, sfr = lane >> 2;
     const int perm_src = (16 * (lane & 3) + (lane >> 2)) * 4;
     size_t obase[KP_NTW];
 #pragma unroll
@@ -456,7 +454,6 @@ igemm_k1t(const TGeom g, const uint4* __restrict__ wpk, const float* __restrict_
       for (int j = (i < NI ? 0 : XJ0); j < (i < NI ? KP_NTW : XJ0 + XJN); ++j) {
         const f32x4 v = i < NI ? acc[i < NI ? i : 0][j] : accx[i < NI ? 0 : j - XJ0];
         f32x4 vs = v * sc;
-#if KP_EPI_PERM
         {   // (the components through a plain struct: ext_vector component reads have miscompiled to component 0 here, see DESIGN)
             struct F4 { float a, b, c, d; };
             const F4 t4 = __builtin_bit_cast(F4, vs);
@@ -466,7 +463,6 @@ igemm_k1t(const TGeom g, const uint4* __restrict__ wpk, const float* __restrict_
           const float p3 = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(perm_src, __builtin_bit_cast(int, t4.d)));
           vs = f32x4{p0, p1, p2, p3};
         }
-#endif
         if (ms < g.M) {
           f32x4* dst = reinterpret_cast<f32x4*>(orow + obase[j]);
           *dst = g.acc ? *dst + vs : vs;

@@ -30,11 +30,6 @@
 // offset differs across a wave 0.83, this version see DESIGN.
 #pragma once
 
-#ifndef WP_DIAG
-#define WP_DIAG 0     // timing-only diagnostic builds (wrong results): bit 0 = producers only synchronise after the prologue,
-#endif                // bit 1 = consumers only synchronise, bit 2 = no memory traffic (all loads out of range), bit 3 = consumers
-                      // read their fragments but issue no products, bit 4 = producers store the raw bits (no split work)
-
 namespace cstp {
 
 constexpr int WP_RING = 512;          // x ring rows (8 segments of 64)
@@ -114,7 +109,6 @@ igemm_k2p(const WPGeom g, const float* __restrict__ dy, const float* __restrict_
       const unsigned fl = __umulhi(L, g.mg_hp1), ll = L - fl * HP1;
       const unsigned f = f_begin + fl, nb = D == 1 ? f : __umulhi(f, g.mg_d), d = f - nb * D;
       const bool ok = fl < (unsigned)F && ll >= 1 && c >= 1 && c <= (unsigned)W;
-      if (WP_DIAG & 4) return OOB;       // (diagnostic: no memory traffic)
       return ok ? ((nb * g.M * D + d) * HW + (ll - 1) * W + (c - 1)) * 4u : OOB;
     };
     // x stream: columns 0, 1 are halo; line 0 of a frame's span is the LAST image line of the previous frame, line 1 the
@@ -127,7 +121,6 @@ igemm_k2p(const WPGeom g, const float* __restrict__ dy, const float* __restrict_
       const unsigned f = f_begin + fl - (prev ? 1u : 0u), nb = D == 1 ? f : __umulhi(f, g.mg_d), d = f - nb * D;
       const unsigned h = prev ? (unsigned)(H - 1) : ll - 2;
       const bool ok = c >= 2 && (prev ? (fl >= 1 && fl <= (unsigned)F) : (ll >= 2 && fl < (unsigned)F));
-      if (WP_DIAG & 4) return OOB;
       return ok ? ((nb * g.C * D + d) * HW + h * W + (c - 2)) * 4u : OOB;
     };
     // channels past the tensors' last ones are CLAMPED (finite values whose products land in slab cells nobody reads);
@@ -173,13 +166,8 @@ igemm_k2p(const WPGeom g, const float* __restrict__ dy, const float* __restrict_
 #pragma unroll
       for (int i = 0; i < 9; ++i) {
         unsigned h0, l0, h1, l1;
-        if (WP_DIAG & 16) {      // (diagnostic: no split work)
-          h0 = __builtin_bit_cast(unsigned, R.a[4 * i]); l0 = __builtin_bit_cast(unsigned, R.a[4 * i + 1]);
-          h1 = __builtin_bit_cast(unsigned, R.a[4 * i + 2]); l1 = __builtin_bit_cast(unsigned, R.a[4 * i + 3]);
-        } else {
-          split2h(R.a[4 * i], R.a[4 * i + 1], sc_dy, h0, l0);
-          split2h(R.a[4 * i + 2], R.a[4 * i + 3], sc_dy, h1, l1);
-        }
+        split2h(R.a[4 * i], R.a[4 * i + 1], sc_dy, h0, l0);
+        split2h(R.a[4 * i + 2], R.a[4 * i + 3], sc_dy, h1, l1);
         const int pj = 9 * pw + i;                    // piece of the 144-channel row: row tile pj / 4, piece pj % 4
         uint2* sub = img + (pj >> 2) * 256 + (a_rb | (((pj & 3) ^ a_xr) << 2));
         sub[0] = make_uint2(h0, h1);
@@ -208,16 +196,12 @@ igemm_k2p(const WPGeom g, const float* __restrict__ dy, const float* __restrict_
     issue(R0);
     __syncthreads();
     for (int i = 0; i < NI; i += 2) {
-#if !(WP_DIAG & 1)
       store(1, i + 1, R1);
       issue(R1);
-#endif
       __syncthreads();
       if (i + 1 >= NI) break;
-#if !(WP_DIAG & 1)
       store(0, i + 2, R0);
       issue(R0);
-#endif
       __syncthreads();
     }
     return;
@@ -238,9 +222,7 @@ igemm_k2p(const WPGeom g, const float* __restrict__ dy, const float* __restrict_
   // dY fragments: my two slots inside a sub-image; row tile m / plane pl add the compile-time offset (2 m + pl) * 128
   const int a_lo = wp_aslot(r_lo, lp), a_hi = wp_aslot(r_hi, lp);
 
-#ifndef WP_NOPRIO
   __builtin_amdgcn_s_setprio(2);
-#endif
   auto body = [&](auto th_tag) __attribute__((always_inline)) {
     constexpr int TH = decltype(th_tag)::value;
     // my five taps 4 * TH .. 4 * TH + 4: ring slot (hi plane) of my k-rows r_lo / r_hi, swizzle included; a K-step moves
@@ -272,12 +254,6 @@ igemm_k2p(const WPGeom g, const float* __restrict__ dy, const float* __restrict_
           return tr2(A + (2 * m + pl) * 128 + a_lo, A + (2 * m + pl) * 128 + a_hi);
         };
         s16x8 b[5][2];
-#if WP_DIAG & 2
-        {       // (diagnostic: one fragment read per K-step keeps the staging stores alive, no products)
-          const s16x8 v0 = tr2(Xr[0] + I_lo[0], Xr[1] + I_hi[0]), v1 = a_frag(0, 0), v2 = a_frag(1, 8);
-          asm volatile("" :: "v"(v0), "v"(v1), "v"(v2));
-        }
-#else
 #pragma unroll
         for (int tl = 0; tl < 5; ++tl) {
           b[tl][0] = tr2(Xr[0] + I_lo[tl], Xr[0] + I_hi[tl]);
@@ -293,10 +269,8 @@ igemm_k2p(const WPGeom g, const float* __restrict__ dy, const float* __restrict_
           // lo * hi, hi * lo, hi * hi (smallest first); the taps inner, so that dependent products are five apart
 #define CSTP_MM(A_, Q)                                                                                              \
   _Pragma("unroll") for (int tl = 0; tl < 5; ++tl)                                                                  \
-    if (wp_mine<TH>(tl, m)) {                                                                                       \
-      if (WP_DIAG & 8) asm volatile("" :: "v"(A_), "v"(b[tl][Q]));                                                  \
-      else acc[tl][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, A_), __builtin_bit_cast(f16x8, b[tl][Q]), acc[tl][m], 0, 0, 0); \
-    }
+    if (wp_mine<TH>(tl, m))                                                                                         \
+      acc[tl][m] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, A_), __builtin_bit_cast(f16x8, b[tl][Q]), acc[tl][m], 0, 0, 0);
           CSTP_MM(f_lo, 0)
           if (m + 1 < 9) f_lo = a_frag(1, m + 1);
           CSTP_MM(f_hi, 1)
@@ -304,7 +278,6 @@ igemm_k2p(const WPGeom g, const float* __restrict__ dy, const float* __restrict_
           if (m + 1 < 9) f_hi = a_frag(0, m + 1);
 #undef CSTP_MM
         }
-#endif
       }
       __syncthreads();
     }

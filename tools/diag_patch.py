@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time the patch kernel alone (cells and packed weights prepared once per call by the library; absmax cell handed in so no
-measuring pass runs) -- for diagnostic library variants (CSTP_LIB_PATH).  usage: diag_patch.py [S1|S3|S5] [fwd|fwdbn|dgrad]
+measuring pass runs), on the in-tree library or on a variant built by tools/build_variant.sh (CSTP_LIB_PATH).  usage: diag_patch.py [S1|S3|S5] [fwd|fwdbn|dgrad]
 (fwdbn: the forward as the training step issues it -- igemm_k1p<MT, true>, BatchNorm sums and range of two view groups from the epilogue)"""
 import ctypes
 import os
@@ -56,17 +56,3 @@ gf = 2.0 * xs[0] * xs[2] * xs[3] * xs[4] * k * xs[1] * (3 if temporal else 9) / 
 print("%s %s tile %s lib %s: min %.3f ms med %.3f ms  %.1f TF/s (incl. %s pack)" % (
     name, "dgrad" if mode else ("fwdbn" if bn else "fwd"), tile, os.path.basename(os.environ.get("CSTP_LIB_PATH", "default")), min(ts),
     sorted(ts)[2], gf / min(ts), "weight"))
-
-if hasattr(lib, "cstp_debug_stamps"):          # a -DKP_DIAG=16 build: in-kernel stamps of consumer wave 0 of block 0
-    import ctypes as C
-    buf = (C.c_ulonglong * 8)()
-    lib.cstp_debug_stamps(buf)                 # reset
-    fn()
-    torch.cuda.synchronize()
-    lib.cstp_debug_stamps(buf)
-    loop, bar, a, epi, kts, items, real = [int(v) for v in buf][:7]
-    whole = int(buf[7])
-    print("stamps (one launch, wave 0 of block 0): %d items, %d K-tiles; per K-tile %.0f cycles, of which barrier wait %.0f, "
-          "A-fragment wait %.0f; epilogue %.0f cycles per item; whole item %.0f cycles (K loops %.0f); clock %.2f GHz"
-          % (items, kts, loop / max(kts, 1), bar / max(kts, 1), a / max(kts, 1), epi / max(items, 1),
-             whole / max(items, 1), loop / max(items, 1), loop / max(real, 1) * 0.1))
