@@ -1,4 +1,4 @@
-// Pooling, loss heads and the per-step flat-arena utilities (EMA, grad-norm clip, SGD).
+// Pooling, loss heads and the per-step flat-arena utilities (EMA, grad-norm clip, SGD, Adam; LARS in lars.h).
 // All HBM-streaming or tiny; fp32 data, fp64 only inside reductions.
 #include "common.h"
 
@@ -572,3 +572,5 @@ extern "C" int cstp_maxpool3d_backward(void* stream, const float* dy, const int3
   CSTP_LAUNCH_CHECK();
   return 0;
 }
+
+#include "lars.h"

@@ -1784,6 +1784,39 @@ def sgd_step_(p, g, buf, lr: torch.Tensor, momentum: float, weight_decay: float,
           "cstp_sgd_step")
 
 
+LARS_CHUNK = 4096         # CSTP_LARS_CHUNK: floats per block of the LARS kernels; optim.lars_tables deals tensors out in these
+
+
+def _lars_tables(chunks: torch.Tensor, segs: torch.Tensor, ratio: torch.Tensor):
+    for t, name in ((chunks, "chunks"), (segs, "segs")):
+        if t.dtype != torch.int32 or t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous() or not t.is_cuda:
+            raise _lib.CstpError("lars %s table must be a contiguous int32 [n, 3] tensor on a HIP device" % name)
+    if ratio.dtype != torch.float32 or ratio.numel() != segs.shape[0] or not ratio.is_contiguous():
+        raise _lib.CstpError("lars ratio must be float32 [%d]" % segs.shape[0])
+
+
+def lars_ratio_(p, g, chunks, segs, weight_decay: float, eta: float, coef: Optional[torch.Tensor], ratio) -> None:
+    """ratio[s] = the trust ratio q of segment s (include/cstp_hip.h: cstp_lars_ratio); two launches, no host read."""
+    lib = _lib.load()
+    _lars_tables(chunks, segs, ratio)
+    assert p.is_cuda and p.numel() == g.numel()
+    ws = _workspace(p.device, lib.cstp_lars_workspace_bytes(chunks.shape[0]))
+    check(lib.cstp_lars_ratio(_stream(), p.data_ptr(), g.data_ptr(), p.numel(), chunks.data_ptr(), chunks.shape[0],
+                              segs.data_ptr(), segs.shape[0], float(weight_decay), float(eta), _ptr(coef), ratio.data_ptr(),
+                              ws.data_ptr(), ws.numel()), "cstp_lars_ratio")
+
+
+def lars_step_(p, g, buf, chunks, segs, ratio, lr: torch.Tensor, momentum: float, weight_decay: float,
+               coef: Optional[torch.Tensor], write_back_grad: bool = True) -> None:
+    """The LARS update of every chunk with its segment's ratio (cstp_lars_step); p, g, buf are the WHOLE arenas."""
+    lib = _lib.load()
+    _lars_tables(chunks, segs, ratio)
+    assert p.is_cuda and p.numel() == g.numel() == buf.numel()
+    check(lib.cstp_lars_step(_stream(), p.data_ptr(), g.data_ptr(), buf.data_ptr(), p.numel(), chunks.data_ptr(), chunks.shape[0],
+                             segs.data_ptr(), segs.shape[0], ratio.data_ptr(), lr.data_ptr(), float(momentum),
+                             float(weight_decay), _ptr(coef), 1 if write_back_grad else 0), "cstp_lars_step")
+
+
 def adam_step_(p, g, exp_avg, exp_avg_sq, lr: torch.Tensor, beta1: float, beta2: float, eps: float, weight_decay: float,
                decoupled: bool, step: int) -> None:
     lib = _lib.load()

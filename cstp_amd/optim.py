@@ -9,6 +9,8 @@ flat parameter/gradient arenas instead of ~170 x 3 tiny launches:
     sumsq(grad arena) -> clip coefficient (stays on the device, no host sync) -> fused scale + weight-decay +
     momentum + update, one launch per RUN of consecutive trainable tensors that share hyper-parameters
     (pre-training / ft_all / scratch: one run = the whole arena; ft_fc: one run = classify.weight|bias).
+FlatLARS (--optimizer lars) is the one optimizer here the reference does not have: per-tensor trust ratios need a reduction per
+tensor, which three launches per run over chunk tables do (csrc/lars.h).
 """
 from __future__ import annotations
 
@@ -201,8 +203,116 @@ class FlatAdam(_FlatOptimizer):
                     g[k] = tuple(sg[k]) if k == "betas" else sg[k]
 
 
+def lars_tables(slots, chunk):
+    """The two tables of csrc/lars.h for the trainable tensors ``slots`` = [(offset, numel, adapted)] of one arena (offsets in
+    floats, multiples of 4; frozen tensors are simply not listed): every tensor's extent, padded to four floats, is cut into
+    chunks of at most ``chunk`` floats that never cross a tensor.
+      -> chunks [(segment, offset, length)], segs [(first chunk, chunk count, adapted 0 / 1)], segment s being slots[s].
+    Pure host code."""
+    if chunk <= 0 or chunk % 4:
+        raise ValueError("chunk must be a positive multiple of 4, got %r" % (chunk,))
+    chunks, segs = [], []
+    for s, (off, numel, adapted) in enumerate(slots):
+        if off < 0 or off % 4 or numel <= 0:
+            raise ValueError("tensor %d: offset %d / numel %d (offsets are multiples of 4 floats, tensors not empty)" % (s, off, numel))
+        end = off + _pad4(numel)
+        if end >= 1 << 31:
+            raise ValueError("tensor %d ends at float %d: the tables hold int32 offsets (arena of 2^31 floats or more)" % (s, end))
+        first = len(chunks)
+        for o in range(off, end, chunk):
+            chunks.append((s, o, min(chunk, end - o)))
+        segs.append((first, len(chunks) - first, 1 if adapted else 0))
+    return chunks, segs
+
+
+class FlatLARS(_FlatOptimizer):
+    """LARS on the flat arenas: SGD with momentum in which each weight tensor's step is scaled by the trust ratio
+    ``q = eta * ||w|| / ||g + weight_decay * w||`` (``q = 1`` when either norm is zero; no eps).
+
+    This is the variant of the published BYOL-family PyTorch code, and it DEPARTS from FlatSGD on purpose: FlatSGD follows the
+    reference and decays every tensor; here tensors with ``dim() <= 1`` (biases, BatchNorm gamma / beta) get neither weight
+    decay nor the adaptation -- for them it is plain SGD with momentum.  Per tensor, with c the pending clip coefficient:
+        g <- c*g (written back to .grad);  d = q*(g + wd*p) if p.dim() > 1 else g;  buf <- momentum*buf + d;  p <- p - lr*buf
+    Norms are taken over the whole tensor, accumulated in double; under DDP they are taken after the gradient all-reduce and
+    are the same on every rank (no collective is added).  Three launches per run of ``_plan()``, no host sync, no atomics:
+    two steps from equal state give equal bits (csrc/lars.h).  ``trust_ratios()`` returns the last step's q."""
+
+    _hyper = ("lr", "momentum", "weight_decay", "eta")
+
+    def __init__(self, params, lr, momentum=0.9, weight_decay=0.0, eta=1e-3, arenas=None):
+        params = list(params)       # frozen tensors stay listed, as in FlatSGD
+        # the torch.optim.SGD group keys ride along, as in FlatSGD: a LARS checkpoint loads into torch.optim.SGD (eta is carried too)
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=0, weight_decay=weight_decay, nesterov=False,
+                                      maximize=False, foreach=None, differentiable=False, fused=None, eta=eta), arenas)
+        if self._p.numel() >= 1 << 31:
+            raise ValueError("FlatLARS: the arena holds %d floats; the chunk tables hold int32 offsets (< 2^31)" % self._p.numel())
+        self._buf = torch.zeros_like(self._p)
+        self._steps = 0
+        self._tables_key, self._tables = None, []
+
+    def _run_tables(self):
+        """Per run of _plan(): (group, chunks, segs, ratio, slot indices) as device tensors, rebuilt when the plan's key changes."""
+        runs = self._plan()
+        if self._tables_key is not None and self._tables_key == self._runs_key:
+            return self._tables
+        dev = self._p.device
+        live = sorted((s[1], i) for i, s in enumerate(self._slots) if s[1] >= 0 and s[4].requires_grad)
+        tables = []
+        for off, n, g, _ in runs:
+            idx = [i for o, i in live if off <= o < off + n]
+            chunks, segs = lars_tables([(self._slots[i][1], self._slots[i][3], self._slots[i][4].dim() > 1) for i in idx],
+                                       ops.LARS_CHUNK)
+            tables.append((g, torch.tensor(chunks, dtype=torch.int32, device=dev), torch.tensor(segs, dtype=torch.int32, device=dev),
+                           torch.ones(len(segs), dtype=torch.float32, device=dev), torch.tensor(idx, dtype=torch.int64, device=dev)))
+        self._tables_key, self._tables = self._runs_key, tables
+        return tables
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        coef = self._coef if self._clip_pending else None
+        for g, chunks, segs, ratio, _ in self._run_tables():
+            ops.lars_ratio_(self._p, self._g, chunks, segs, g["weight_decay"], g["eta"], coef, ratio)
+            ops.lars_step_(self._p, self._g, self._buf, chunks, segs, ratio, self._lr_tensor(float(g["lr"])), g["momentum"],
+                           g["weight_decay"], coef, True)
+        self._clip_pending = False
+        self._steps += 1
+
+    def trust_ratios(self):
+        """-> (q [n_tensors] on the device, parameter indices [n_tensors]): the trust ratio each tensor took in the last step, in
+        the order of the parameter list (= state_dict indices): 1 for the tensors that are not adapted, NaN for frozen ones
+        (and for every tensor before the first step).  No host read."""
+        q = torch.full((len(self._slots),), float("nan"), dtype=torch.float32, device=self._p.device)
+        if self._steps > 0:
+            for _, _, _, ratio, idx in self._run_tables():
+                q[idx] = ratio
+        return q, torch.arange(len(self._slots), device=self._p.device)
+
+    # checkpoint wire format of torch.optim.SGD, as FlatSGD writes it (main_byol.py:132-140 saves optimizer.state_dict())
+    def state_dict(self):
+        sd = super().state_dict()
+        state = {}
+        for i, (_, off, _, numel, p) in enumerate(self._slots):
+            if self._steps > 0 and p.requires_grad and off >= 0:
+                state[i] = {"momentum_buffer": self._buf[off:off + numel].view_as(p).clone()}
+        sd["state"] = state
+        return sd
+
+    def load_state_dict(self, sd):
+        loaded = False
+        for i, (_, off, _, numel, p) in enumerate(self._slots):
+            st = sd["state"].get(i, sd["state"].get(str(i)))
+            if st is not None and st.get("momentum_buffer") is not None and off >= 0:
+                self._buf[off:off + numel].view_as(p).copy_(st["momentum_buffer"])
+                loaded = True
+        self._steps = 1 if loaded else 0
+        for g, sg in zip(self.param_groups, sd["param_groups"]):
+            for k in ("lr", "momentum", "weight_decay", "eta"):
+                if k in sg:
+                    g[k] = sg[k]
+
+
 def build_optimizer(opts, parameters, arenas):
-    """main_byol.py:227-244 / main_ft_mp.py:132-147: --optimizer sgd | adam | adamw."""
+    """main_byol.py:227-244 / main_ft_mp.py:132-147: --optimizer sgd | adam | adamw; lars is this package's addition."""
     if opts.optimizer == "sgd":
         return FlatSGD(parameters, lr=opts.learning_rate, momentum=opts.momentum, weight_decay=opts.weight_decay,
                        arenas=arenas)
@@ -211,4 +321,7 @@ def build_optimizer(opts, parameters, arenas):
                         decoupled=True, arenas=arenas)
     if opts.optimizer == "adam":
         return FlatAdam(parameters, lr=opts.learning_rate, weight_decay=opts.weight_decay, arenas=arenas)
-    raise ValueError("unknown --optimizer %r (sgd / adam / adamw)" % (opts.optimizer,))
+    if opts.optimizer == "lars":
+        return FlatLARS(parameters, lr=opts.learning_rate, momentum=opts.momentum, weight_decay=opts.weight_decay,
+                        eta=opts.lars_eta, arenas=arenas)
+    raise ValueError("unknown --optimizer %r (sgd / adam / adamw / lars)" % (opts.optimizer,))

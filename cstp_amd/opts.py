@@ -12,6 +12,8 @@ Additions (all optional, defaults reproduce the reference):
                     3D-ResNet-50, bf16; both backbones -- cstp_amd/r3d_byol.py, cstp_amd/r21d_byol.py)
   --retrieval_k     the k of R@k for the retrieval driver (retrieval.py), each in 1..64 (default 1 5 10 20 50)
   --retrieval_gallery_len   gallery videos of --dataset synthetic_video in the retrieval driver (queries: --synthetic_len / 4)
+  --lars_eta        trust coefficient of --optimizer lars (default 1e-3): each weight tensor's step is scaled by
+                    eta * ||w|| / ||g + weight_decay * w||; biases and BatchNorm parameters are neither decayed nor adapted
 torchrun passes LOCAL_RANK through the environment instead of --local_rank; both are honoured.
 """
 from __future__ import annotations
@@ -54,7 +56,8 @@ _FLAGS = [
     ("dampening", 0.9, float, "accepted for compatibility; the reference never passes it to SGD"),
     ("weight_decay", 1e-4, float, "weight decay"),
     ("nesterov", False, None, "accepted for compatibility; unused by the reference driver"),
-    ("optimizer", "sgd", str, "sgd | adamw | adam (flat-arena HIP kernels)"),
+    ("optimizer", "sgd", str, "sgd | adamw | adam | lars (flat-arena HIP kernels; lars: SGD with momentum and per-tensor trust "
+     "ratios, see --lars_eta)"),
     ("lr_patience", 10, int, "ReduceLROnPlateau patience (fine-tune only)"),
     ("n_epochs", 400, int, "epochs"),
     # logging / misc
@@ -98,6 +101,7 @@ _FLAGS = [
     ("bucket_cap_mb", 25, int, "DDP gradient bucket size in MB"),
     ("act_dtype", "fp32", str, "fp32 | bf16: activation storage type (r21d_byol and r3d_byol; s3d_byol and i3d_byol are fp32 only)"),
     ("retrieval_gallery_len", 64, int, "retrieval.py with --dataset synthetic_video: number of gallery videos"),
+    ("lars_eta", 1e-3, float, "--optimizer lars: trust coefficient eta of the per-tensor ratio eta * |w| / |g + weight_decay * w|"),
 ]
 RETRIEVAL_MAX_K = 64      # ops.SIM_TOPK_MAX_K: one lane per list slot
 

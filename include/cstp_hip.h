@@ -437,6 +437,32 @@ int cstp_sgd_step(void* stream, float* p, float* g, float* buf, size_t n, const 
 int cstp_adam_step(void* stream, float* p, const float* g, float* exp_avg, float* exp_avg_sq, size_t n, const float* lr,
                    float beta1, float beta2, float eps, float weight_decay, int32_t decoupled, int32_t step);
 
+/* LARS (SGD with momentum whose step is scaled per tensor by a trust ratio), the variant of the published BYOL-family PyTorch
+ * code: no eps in the ratio, tensors with dim() <= 1 (biases, BatchNorm gamma / beta) get neither weight decay nor adaptation.
+ * Per tensor, c = coef[0] (1 when coef is NULL):
+ *   g <- c*g                                  (written back when write_back_grad)
+ *   adapted:     d = g + wd*p;  wn = ||p||_2, dn = ||d||_2 over the whole tensor (accumulated in double);
+ *                q = eta*wn/dn if wn > 0 and dn > 0 else 1;  d = q*d
+ *   not adapted: d = g;  q = 1
+ *   buf <- momentum*buf + d;   p <- p - lr[0]*buf          (buf starts at zero; lr is a DEVICE scalar)
+ * The tensors of one call are described by two DEVICE int32 tables over arenas p / g / buf of n floats (n < 2^31):
+ *   chunks [n_chunks][3] = {segment, offset, length}: a run of floats of ONE tensor, offset and length multiples of 4 (tensors
+ *                          start on 16-byte boundaries and are zero-padded to four floats; the padding belongs to the chunk and
+ *                          stays zero), length <= CSTP_LARS_CHUNK; the chunks of a segment are consecutive
+ *   segs   [n_segs][3]   = {first chunk, chunk count, adapted}: one tensor
+ * One block per chunk.  cstp_lars_ratio: two launches (chunk partials into ws, then a fixed-order sum per segment) ->
+ * ratio[n_segs] = q.  cstp_lars_step: one launch, the update with those q.  No atomics, no host read: equal inputs give equal
+ * bits.  A table entry that points outside the arena or the tables is skipped, not followed. */
+#define CSTP_LARS_CHUNK 4096
+int cstp_lars_chunk(void);                          /* CSTP_LARS_CHUNK of the built library */
+size_t cstp_lars_workspace_bytes(int32_t n_chunks); /* two doubles per chunk; 0 for n_chunks <= 0 */
+int cstp_lars_ratio(void* stream, const float* p, const float* g, size_t n, const int32_t* chunks, int32_t n_chunks,
+                    const int32_t* segs, int32_t n_segs, float weight_decay, float eta, const float* coef, float* ratio, void* ws,
+                    size_t ws_bytes);
+int cstp_lars_step(void* stream, float* p, float* g, float* buf, size_t n, const int32_t* chunks, int32_t n_chunks,
+                   const int32_t* segs, int32_t n_segs, const float* ratio, const float* lr, float momentum, float weight_decay,
+                   const float* coef, int32_t write_back_grad);
+
 /* ---- the bf16-STORAGE path (BASELINE configs[4]: 3D-ResNet-50 backbone swap, bf16) --------------------------------
  * The ATen call-sites of models/BE/r3d_byol.py under bf16 activations (what torch.autocast(bfloat16) makes of them): every
  * 5-D activation tensor and every gradient of one is bf16 in HBM (uint16_t* below = raw bf16 bits, NCDHW, contiguous), all

@@ -155,7 +155,7 @@ def main_worker(local_rank, opts):
         overlay=not opts.resume_md_path) \
         if local_rank == 0 else None
 
-    optimizer = build_optimizer(opts, parameters, inner.flatten_parameters())   # sgd | adamw | adam (main_byol.py:227-244)
+    optimizer = build_optimizer(opts, parameters, inner.flatten_parameters())   # sgd | adamw | adam (main_byol.py:227-244) | lars
     begin_epoch = 1
     if opts.resume_md_path:
         # The reference only reloads the optimizer for --task resume and then trains nothing (main_byol.py:246-247,
