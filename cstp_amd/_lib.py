@@ -45,6 +45,12 @@ class BncBranch(ctypes.Structure):
                 ("c", c_int32), ("nsplit", c_int32)]
 
 
+class ClipMixEntry(ctypes.Structure):
+    """struct cstp_clip_mix_entry: one sample of a mixup / CutMix launch (cstp_clip_mix)."""
+    _fields_ = [("partner", c_int32), ("mode", c_int32), ("lam", c_float), ("y0", c_int32), ("y1", c_int32), ("x0", c_int32),
+                ("x1", c_int32), ("reserved", c_int32)]
+
+
 class CstpError(RuntimeError):
     pass
 
@@ -116,6 +122,8 @@ SIGNATURES = {
     "cstp_l2_normalize_backward": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int32, c_float]),
     "cstp_cross_entropy_forward": (c_int32, [_P, _P, _P, _P, c_int32, c_int32]),
     "cstp_cross_entropy_backward": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int32]),
+    "cstp_soft_cross_entropy_forward": (c_int32, [_P, _P, _P, _P, _P, c_float, _P, c_int32, c_int32]),
+    "cstp_soft_cross_entropy_backward": (c_int32, [_P, _P, _P, _P, _P, c_float, _P, _P, c_int32, c_int32]),
     "cstp_ntxent_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "cstp_ntxent_forward": (c_int32, [_P, _P, _P, c_int32, c_int32, c_float, _P, c_size_t]),
     "cstp_ntxent_backward": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_float, _P, c_size_t]),
@@ -132,6 +140,7 @@ SIGNATURES = {
     "cstp_clip_batch_desc_bytes": (c_size_t, []),
     "cstp_clip_batch_forward": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, _P, c_int32, _P, c_int64, _P, c_int32, _P,
                                           c_int32]),
+    "cstp_clip_mix": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32]),
     "cstp_ema_update": (c_int32, [_P, _P, _P, c_size_t, c_double]),
     "cstp_sumsq": (c_int32, [_P, _P, c_size_t, _P, _P, c_size_t]),
     "cstp_clip_coef": (c_int32, [_P, _P, c_float, _P, _P]),

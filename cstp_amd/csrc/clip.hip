@@ -13,6 +13,7 @@
 // The fine-tune / validation / video-test clips (datasets.py:952-1097 UcfFineTune, preprocess_data.py:1131-1149) come a BATCH at a
 // time through cstp_clip_batch_forward at the end of this file: one descriptor table, two launches for any number of clips.
 // A batch of pre-training pairs takes the same road, with a rotation code per clip (clip_ops.assemble_pairs).
+// Last in the file: cstp_clip_mix, mixup / CutMix of an assembled fp32 batch for fine-tuning (one launch, one table entry per sample).
 #include "common.h"
 
 namespace cstp {
@@ -534,6 +535,83 @@ extern "C" int cstp_clip_batch_forward(void* stream, const cstp_clip_batch_desc*
   CSTP_LAUNCH_CHECK();
   hipLaunchKernelGGL(clip_batch_v_kernel, dim3((unsigned)(bv_ > 2048 ? 2048 : bv_), n), dim3(256), 0, s, desc_dev, tmp, out, out8, t,
                      size);
+  CSTP_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- mixup / CutMix over a batch of fp32 clips (fine-tuning: cstp_amd/mix.py) -------------------------------------------------
+// x, y: [b][planes][h][w]; one launch, blockIdx.y = sample, its table entry read by every block that serves it.  The entry is
+// checked where it is used -- partner in [0, b), known mode, box inside the frame -- and a malformed one is served as a copy,
+// never followed (the rule of the LARS tables, lars.h).  A sample that is its own partner is a copy too: exact, whatever lam.
+// VEC: w % 4 == 0 and both bases 16-byte aligned, so every sample and every row starts on a 16-byte boundary and a float4
+// group never straddles a row; a box edge inside a group is resolved per element.  CutMix copies bits (no arithmetic).
+namespace cstp {
+
+template <bool VEC>
+__global__ void __launch_bounds__(256) clip_mix_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                       const cstp_clip_mix_entry* __restrict__ table, int b, int planes, int h,
+                                                       int w) {
+  const int i = blockIdx.y;
+  const cstp_clip_mix_entry e = table[i];
+  int mode = e.mode;
+  const bool ok = e.partner >= 0 && e.partner < b && (mode == 1 || mode == 2) && e.y0 >= 0 && e.y0 <= e.y1 && e.y1 <= h &&
+                  e.x0 >= 0 && e.x0 <= e.x1 && e.x1 <= w;
+  if (!ok || e.partner == i) mode = 0;
+  const int partner = mode ? e.partner : i;
+  const size_t n = (size_t)planes * h * w;
+  const float* __restrict__ xs = x + (size_t)i * n;
+  const float* __restrict__ xp = x + (size_t)partner * n;
+  float* __restrict__ ys = y + (size_t)i * n;
+  const float lam = e.lam, rem = 1.f - e.lam;
+  if (VEC) {
+    const size_t groups = n >> 2;
+    const int wg = w >> 2;
+    for (size_t g = (size_t)blockIdx.x * 256 + threadIdx.x; g < groups; g += (size_t)gridDim.x * 256) {
+      float4 v = reinterpret_cast<const float4*>(xs)[g];
+      if (mode == 1) {
+        const float4 p = reinterpret_cast<const float4*>(xp)[g];
+        v.x = lam * v.x + rem * p.x; v.y = lam * v.y + rem * p.y; v.z = lam * v.z + rem * p.z; v.w = lam * v.w + rem * p.w;
+      } else if (mode == 2) {
+        const int col = (int)(g % wg) << 2, row = (int)((g / wg) % h);
+        if (row >= e.y0 && row < e.y1 && col + 4 > e.x0 && col < e.x1) {
+          const float4 p = reinterpret_cast<const float4*>(xp)[g];
+          if (col >= e.x0 && col < e.x1) v.x = p.x;
+          if (col + 1 >= e.x0 && col + 1 < e.x1) v.y = p.y;
+          if (col + 2 >= e.x0 && col + 2 < e.x1) v.z = p.z;
+          if (col + 3 >= e.x0 && col + 3 < e.x1) v.w = p.w;
+        }
+      }
+      reinterpret_cast<float4*>(ys)[g] = v;
+    }
+  } else {
+    for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < n; j += (size_t)gridDim.x * 256) {
+      float v = xs[j];
+      if (mode == 1) {
+        v = lam * v + rem * xp[j];
+      } else if (mode == 2) {
+        const int col = (int)(j % w), row = (int)((j / w) % h);
+        if (row >= e.y0 && row < e.y1 && col >= e.x0 && col < e.x1) v = xp[j];
+      }
+      ys[j] = v;
+    }
+  }
+}
+
+}  // namespace cstp
+
+extern "C" int cstp_clip_mix(void* stream, const float* x, float* y, const cstp_clip_mix_entry* table, int32_t b, int32_t planes,
+                             int32_t h, int32_t w) {
+  static_assert(sizeof(cstp_clip_mix_entry) == 32, "cstp_clip_mix_entry is packed by the host as 32 bytes");
+  CSTP_REQUIRE(x && y && table, "null argument");
+  CSTP_REQUIRE(b > 0 && b <= 65535 && planes > 0 && h > 0 && w > 0, "bad shape");
+  CSTP_REQUIRE((int64_t)b * planes * h * w <= INT32_MAX && (int64_t)planes * h <= INT32_MAX, "bad shape (more than 2^31 - 1 values)");
+  CSTP_REQUIRE(y != x, "y must not alias x");
+  const size_t n = (size_t)planes * h * w;
+  const bool vec = (w % 4) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) % 16) == 0;
+  const size_t units = vec ? n / 4 : n, blocks = (units + 255) / 256;
+  const dim3 grid((unsigned)(blocks > 1024 ? 1024 : blocks), b);
+  if (vec) hipLaunchKernelGGL(clip_mix_kernel<true>, grid, dim3(256), 0, as_stream(stream), x, y, table, b, planes, h, w);
+  else hipLaunchKernelGGL(clip_mix_kernel<false>, grid, dim3(256), 0, as_stream(stream), x, y, table, b, planes, h, w);
   CSTP_LAUNCH_CHECK();
   return 0;
 }

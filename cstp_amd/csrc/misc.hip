@@ -195,6 +195,69 @@ __global__ void ce_bwd_kernel(const float* __restrict__ logits, const int64_t* _
   }
 }
 
+// ---- soft-target CrossEntropy(mean): label smoothing and two weighted targets per row (mixup / CutMix) ----------------
+// q[r][c] = (1-eps)*(lam[r]*[c==ta[r]] + (1-lam[r])*[c==tb[r]]) + eps/k;  loss = mean_r -sum_c q[r][c]*log_softmax(logits[r])[c].
+// One wave per row with the 64 lanes along k (k is 51 / 101 / 400 here); the row statistics come out of xor-shuffles, whose
+// order is fixed, so equal inputs give equal bits.  A target outside [0, k) carries no one-hot mass and is never an index.
+// tb == NULL: tb = ta;  lam == NULL: lam = 1.
+__device__ __forceinline__ void soft_ce_row_stats(const float* __restrict__ p, int k, int lane, float& mx, float& se, float& sp) {
+  float m = -INFINITY;
+  for (int j = lane; j < k; j += 64) m = fmaxf(m, p[j]);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
+  float e = 0.f, s = 0.f;
+  for (int j = lane; j < k; j += 64) { const float v = p[j]; e += expf(v - m); s += v; }
+  mx = m;
+  se = wave_sum_all(e);
+  sp = wave_sum_all(s);
+}
+
+// one block of 1024 threads: wave w takes rows w, w + 16, ...; the batch mean is accumulated in double (as ce_fwd_kernel does)
+__global__ void __launch_bounds__(1024) soft_ce_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ ta,
+                                                           const int64_t* __restrict__ tb, const float* __restrict__ lam,
+                                                           float eps, float* __restrict__ loss, int b, int k) {
+  __shared__ double sm[16];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  double a = 0.0;
+  for (int r = wave; r < b; r += nw) {
+    const float* p = logits + (size_t)r * k;
+    float mx, se, sp;
+    soft_ce_row_stats(p, k, lane, mx, se, sp);
+    if (lane == 0) {
+      const float lse = logf(se) + mx;
+      const int64_t a_ = ta[r], b_ = tb ? tb[r] : a_;
+      const float l = lam ? lam[r] : 1.f;
+      const float na = (a_ >= 0 && a_ < k) ? lse - p[a_] : 0.f;
+      const float nb = (b_ >= 0 && b_ < k) ? lse - p[b_] : 0.f;
+      a += (double)((1.f - eps) * (l * na + (1.f - l) * nb) + eps * (lse - sp / (float)k));
+    }
+  }
+  a = block_sum(a, sm);
+  if (threadIdx.x == 0) loss[0] = (float)(a / b);
+}
+
+// dlogits = dloss[0] * (softmax * sum_c q - q) / b (sum_c q = 1 unless a target lies outside); four rows per block, one wave each
+__global__ void __launch_bounds__(256) soft_ce_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ ta,
+                                                          const int64_t* __restrict__ tb, const float* __restrict__ lam,
+                                                          float eps, const float* __restrict__ dloss,
+                                                          float* __restrict__ dlogits, int b, int k) {
+  const int lane = threadIdx.x & 63, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= b) return;
+  const float* p = logits + (size_t)r * k;
+  float mx, se, sp;
+  soft_ce_row_stats(p, k, lane, mx, se, sp);
+  const float gscale = dloss[0] / (float)b, inv = 1.f / se;
+  const int64_t a_ = ta[r], b_ = tb ? tb[r] : a_;
+  const float l = lam ? lam[r] : 1.f;
+  const float wa = (1.f - eps) * l, wb = (1.f - eps) * (1.f - l), u = eps / (float)k;
+  // sum_c q: exactly 1 with both targets inside [0, k); a target outside takes its mass out of the row (and of softmax's weight)
+  const float qs = 1.f - ((a_ >= 0 && a_ < k) ? 0.f : wa) - ((b_ >= 0 && b_ < k) ? 0.f : wb);
+  for (int j = lane; j < k; j += 64) {
+    const float q = (j == a_ ? wa : 0.f) + (j == b_ ? wb : 0.f) + u;
+    dlogits[(size_t)r * k + j] = gscale * (qs * (expf(p[j] - mx) * inv) - q);
+  }
+}
+
 // ---- NT-Xent ---------------------------------------------------------------------------------------
 // ws layout (floats): norms[2n] | lse[2n] | sim[2n*2n] | G[2n*2n]
 __global__ void ntx_norm_kernel(const float* __restrict__ reps, float* __restrict__ norms, int two_n, int f) {
@@ -447,6 +510,29 @@ extern "C" int cstp_cross_entropy_backward(void* stream, const float* logits, co
                                            float* dlogits, int32_t b, int32_t k) {
   CSTP_REQUIRE(logits && labels && dloss && dlogits && b > 0 && k > 0, "bad argument");
   hipLaunchKernelGGL(ce_bwd_kernel, dim3(cdiv(b, 256)), dim3(256), 0, as_stream(stream), logits, labels, dloss, dlogits, b, k);
+  CSTP_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int cstp_soft_cross_entropy_forward(void* stream, const float* logits, const int64_t* ta, const int64_t* tb,
+                                               const float* lam, float eps, float* loss, int32_t b, int32_t k) {
+  CSTP_REQUIRE(logits && ta && loss, "null argument");
+  CSTP_REQUIRE(b > 0 && k > 0 && (int64_t)b * k <= INT32_MAX, "bad shape");
+  CSTP_REQUIRE(eps >= 0.f && eps < 1.f, "label smoothing outside [0, 1)");
+  hipLaunchKernelGGL(soft_ce_fwd_kernel, dim3(1), dim3(1024), 0, as_stream(stream), logits, ta, tb, lam, eps, loss, b, k);
+  CSTP_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int cstp_soft_cross_entropy_backward(void* stream, const float* logits, const int64_t* ta, const int64_t* tb,
+                                                const float* lam, float eps, const float* dloss, float* dlogits, int32_t b,
+                                                int32_t k) {
+  CSTP_REQUIRE(logits && ta && dloss && dlogits, "null argument");
+  CSTP_REQUIRE(b > 0 && k > 0 && (int64_t)b * k <= INT32_MAX, "bad shape");
+  CSTP_REQUIRE(eps >= 0.f && eps < 1.f, "label smoothing outside [0, 1)");
+  CSTP_REQUIRE(dlogits != logits, "dlogits must not alias logits");
+  hipLaunchKernelGGL(soft_ce_bwd_kernel, dim3(cdiv(b, 4)), dim3(256), 0, as_stream(stream), logits, ta, tb, lam, eps, dloss,
+                     dlogits, b, k);
   CSTP_LAUNCH_CHECK();
   return 0;
 }

@@ -9,10 +9,12 @@ import ctypes
 import os
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
 from ._lib import ConvDesc, InAffine, check
+from .mix import MODE_COPY, MODE_CUTMIX, MODE_MIXUP
 
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
@@ -1689,6 +1691,107 @@ class _CrossEntropy(torch.autograd.Function):
 def cross_entropy(logits, labels):
     """nn.CrossEntropyLoss() (mean reduction)."""
     return _CrossEntropy.apply(logits, labels)
+
+
+class _SoftCrossEntropy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, ta, tb, lam, eps):
+        lib = _lib.load()
+        logits = _req(logits, "soft_cross_entropy logits")
+        if logits.dim() != 2:
+            raise _lib.CstpError("soft_cross_entropy expects logits [batch, classes], got %s" % (tuple(logits.shape),))
+        b, k = logits.shape
+        for name, t in (("ta", ta), ("tb", tb)):
+            if t is not None and (t.dtype != torch.int64 or not t.is_cuda or t.shape != (b,)):
+                raise _lib.CstpError("soft_cross_entropy %s must be int64 [%d] on the HIP device" % (name, b))
+        if lam is not None and (lam.dtype != torch.float32 or not lam.is_cuda or lam.shape != (b,)):
+            raise _lib.CstpError("soft_cross_entropy lam must be float32 [%d] on the HIP device" % b)
+        ta = ta.contiguous()
+        tb = None if tb is None else tb.contiguous()
+        lam = None if lam is None else lam.contiguous()
+        loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+        check(lib.cstp_soft_cross_entropy_forward(_stream(), logits.data_ptr(), ta.data_ptr(), _ptr(tb), _ptr(lam), eps,
+                                                  loss.data_ptr(), b, k), "cstp_soft_cross_entropy_forward")
+        ctx.save_for_backward(logits, ta, tb, lam)
+        ctx.eps = eps
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        lib = _lib.load()
+        logits, ta, tb, lam = ctx.saved_tensors
+        dloss = _req(dloss.reshape(1), "soft_cross_entropy grad_output")
+        dl = torch.empty_like(logits)
+        check(lib.cstp_soft_cross_entropy_backward(_stream(), logits.data_ptr(), ta.data_ptr(), _ptr(tb), _ptr(lam), ctx.eps,
+                                                   dloss.data_ptr(), dl.data_ptr(), logits.shape[0], logits.shape[1]),
+              "cstp_soft_cross_entropy_backward")
+        return dl, None, None, None, None
+
+
+def soft_cross_entropy(logits, ta, tb=None, lam=None, eps=0.0):
+    """Mean cross-entropy against q = (1-eps)*(lam*onehot(ta) + (1-lam)*onehot(tb)) + eps/classes: label smoothing and the two
+    weighted targets of mixup / CutMix (F.cross_entropy(logits, q)).  ta / tb: int64 [batch], lam: fp32 [batch], all on the
+    device; tb = None means tb = ta, lam = None means lam = 1 (the smoothing-only form, F.cross_entropy(logits, ta,
+    label_smoothing=eps)).  A target outside [0, classes) adds no one-hot mass."""
+    eps = float(eps)
+    if not 0.0 <= eps < 1.0:
+        raise _lib.CstpError("soft_cross_entropy eps must lie in [0, 1), got %r" % (eps,))
+    return _SoftCrossEntropy.apply(logits, ta, tb, lam, eps)
+
+
+# struct cstp_clip_mix_entry (include/cstp_hip.h), packed by hand into the pinned upload buffer
+_MIX_ENTRY = np.dtype([("partner", "<i4"), ("mode", "<i4"), ("lam", "<f4"), ("y0", "<i4"), ("y1", "<i4"), ("x0", "<i4"),
+                       ("x1", "<i4"), ("reserved", "<i4")])
+
+
+def _per_sample(v, b, name):
+    v = [v] * b if isinstance(v, (int, float)) else list(v)
+    if len(v) != b:
+        raise _lib.CstpError("clip_mix %s has %d entries for a batch of %d" % (name, len(v), b))
+    return v
+
+
+def clip_mix(x, partner, mode, lam, boxes=None):
+    """mixup / CutMix of a batch of clips in one launch (cstp_clip_mix): x [B, ..., H, W] fp32 -> a new tensor of that shape.
+    Per sample i (host sequences of B entries; ``mode`` and ``lam`` may be one value for all, ``boxes`` one box for all or None):
+    mode 0 copies x[i], mode 1 gives lam*x[i] + (1-lam)*x[partner[i]], mode 2 pastes x[partner[i]] into the half-open box
+    (y0, y1, x0, x1) of every plane.  The table is validated completely here -- a bad entry raises CstpError before anything is
+    uploaded or launched -- and travels in one pinned, asynchronous upload; nothing is read back."""
+    if x.dim() < 3:
+        raise _lib.CstpError("clip_mix expects [batch, ..., height, width], got %s" % (tuple(x.shape),))
+    b, h, w = x.shape[0], x.shape[-2], x.shape[-1]
+    partner = _per_sample(partner, b, "partner")
+    mode = _per_sample(mode, b, "mode")
+    lam = _per_sample(lam, b, "lam")
+    if boxes is None:
+        boxes = (0, 0, 0, 0)
+    if len(boxes) == 4 and all(isinstance(v, (int, np.integer)) for v in boxes):
+        boxes = [boxes] * b
+    boxes = _per_sample(boxes, b, "boxes")
+    for i in range(b):
+        if int(partner[i]) != partner[i] or not 0 <= partner[i] < b:
+            raise _lib.CstpError("clip_mix partner[%d] = %r is outside the batch of %d" % (i, partner[i], b))
+        if mode[i] not in (MODE_COPY, MODE_MIXUP, MODE_CUTMIX):
+            raise _lib.CstpError("clip_mix mode[%d] = %r: 0 (copy), 1 (mixup) and 2 (CutMix) exist" % (i, mode[i]))
+        if not 0.0 <= float(lam[i]) <= 1.0:
+            raise _lib.CstpError("clip_mix lam[%d] = %r is outside [0, 1]" % (i, lam[i]))
+        if len(boxes[i]) != 4 or any(int(v) != v for v in boxes[i]):
+            raise _lib.CstpError("clip_mix boxes[%d] = %r: a box is four integers (y0, y1, x0, x1)" % (i, boxes[i]))
+        y0, y1, x0, x1 = boxes[i]
+        if not (0 <= y0 <= y1 <= h and 0 <= x0 <= x1 <= w):
+            raise _lib.CstpError("clip_mix boxes[%d] = %r leaves the %d x %d frame" % (i, tuple(boxes[i]), h, w))
+    lib = _lib.load()
+    x = _req(x, "clip_mix input")
+    planes = x.numel() // (b * h * w) if x.numel() else 0
+    host = torch.empty(b * _MIX_ENTRY.itemsize, dtype=torch.uint8, pin_memory=True)
+    tab = host.numpy().view(_MIX_ENTRY)
+    for i in range(b):
+        tab[i] = (int(partner[i]), int(mode[i]), float(lam[i])) + tuple(int(v) for v in boxes[i]) + (0,)
+    table = torch.empty(host.numel(), dtype=torch.uint8, device=x.device)
+    table.copy_(host, non_blocking=True)
+    y = torch.empty_like(x)
+    check(lib.cstp_clip_mix(_stream(), x.data_ptr(), y.data_ptr(), table.data_ptr(), b, planes, h, w), "cstp_clip_mix")
+    return y
 
 
 class _NTXent(torch.autograd.Function):

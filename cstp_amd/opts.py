@@ -14,6 +14,13 @@ Additions (all optional, defaults reproduce the reference):
   --retrieval_gallery_len   gallery videos of --dataset synthetic_video in the retrieval driver (queries: --synthetic_len / 4)
   --lars_eta        trust coefficient of --optimizer lars (default 1e-3): each weight tensor's step is scaled by
                     eta * ||w|| / ||g + weight_decay * w||; biases and BatchNorm parameters are neither decayed nor adapted
+  --label_smoothing  fine-tuning (main_ft_mp.py): weight eps of the uniform part of the training target, in [0, 1) (default 0)
+  --mixup_alpha      fine-tuning: mixup with lam ~ Beta(alpha, alpha), one draw per batch (default 0 = off)
+  --cutmix_alpha     fine-tuning: CutMix with lam ~ Beta(alpha, alpha), the box spanning all frames of the clip (default 0 = off)
+  --mix_prob         fine-tuning: probability that a batch is mixed at all (default 1)
+  --mix_switch_prob  fine-tuning: probability of CutMix when both alphas are positive (default 0.5)
+                     (cstp_amd/mix.py; validation keeps the plain cross-entropy; main_byol.py, test.py and retrieval.py
+                     ignore all five)
 torchrun passes LOCAL_RANK through the environment instead of --local_rank; both are honoured.
 """
 from __future__ import annotations
@@ -102,6 +109,11 @@ _FLAGS = [
     ("act_dtype", "fp32", str, "fp32 | bf16: activation storage type (r21d_byol and r3d_byol; s3d_byol and i3d_byol are fp32 only)"),
     ("retrieval_gallery_len", 64, int, "retrieval.py with --dataset synthetic_video: number of gallery videos"),
     ("lars_eta", 1e-3, float, "--optimizer lars: trust coefficient eta of the per-tensor ratio eta * |w| / |g + weight_decay * w|"),
+    ("label_smoothing", 0.0, float, "main_ft_mp.py: label smoothing eps of the training loss, in [0, 1) (0 = hard labels)"),
+    ("mixup_alpha", 0.0, float, "main_ft_mp.py: mixup, lam ~ Beta(alpha, alpha) once per batch (0 = off)"),
+    ("cutmix_alpha", 0.0, float, "main_ft_mp.py: CutMix, lam ~ Beta(alpha, alpha) once per batch, one box through all frames (0 = off)"),
+    ("mix_prob", 1.0, float, "main_ft_mp.py: probability that a batch is mixed (with --mixup_alpha / --cutmix_alpha)"),
+    ("mix_switch_prob", 0.5, float, "main_ft_mp.py: probability of CutMix instead of mixup when both alphas are positive"),
 ]
 RETRIEVAL_MAX_K = 64      # ops.SIM_TOPK_MAX_K: one lane per list slot
 

@@ -309,9 +309,12 @@ class FineTuneStep:
     Returns (loss, outputs) as DEVICE tensors; the caller derives accuracy from ``outputs`` as the reference does.
     Under DDP the per-bucket reducer is bypassed (``no_sync``) and only the trainable runs of the flat gradient arena
     are all-reduced -- for ft_fc that is the 52 K-float classifier instead of the 33 M-float encoder -- and the BN
-    buffers are broadcast from rank 0 at the top of each step (see PretrainStep)."""
+    buffers are broadcast from rank 0 at the top of each step (see PretrainStep).
+    ``mixer`` (cstp_amd.mix.Mixer; None = exactly the step above): per step one plan of (seed, epoch, step, rank) is drawn, the
+    batch is blended in one launch (ops.clip_mix; skipped for an identity plan) and the loss is ops.soft_cross_entropy against the
+    sample's and its partner's labels with the mixer's label smoothing.  Ranks draw different plans; nothing is communicated."""
 
-    def __init__(self, model, optimizer, task, flat_allreduce=True, cross_entropy=None):
+    def __init__(self, model, optimizer, task, flat_allreduce=True, cross_entropy=None, mixer=None):
         self._ce = cross_entropy if cross_entropy is not None else ops.cross_entropy
         if task not in ("ft_fc", "ft_all"):
             raise ValueError("o_type %r: the classifier forward serves 'ft_fc' / 'ft_all' (r21d_byol.py:394)" % (task,))
@@ -322,14 +325,51 @@ class FineTuneStep:
         self._g = arenas["grad"] if arenas is not None else None
         ops.mark_direct_grad(inner, arenas, arenas is not None and (self._flat or not hasattr(model, "no_sync")))
         self._tiles_shared = False
+        # label smoothing / mixup / CutMix (cstp_amd/mix.py); None: the step above, untouched
+        self.mixer = mixer
+        self._epoch, self._step = 0, 0
+        self.last_plan = None
+
+    def set_epoch(self, epoch):
+        """Positions the mixer's plans: they are functions of (seed, epoch, step within the epoch, rank), so a resumed run that
+        starts at its begin_epoch draws what the uninterrupted run drew."""
+        self._epoch, self._step = int(epoch), 0
+
+    def accuracy_targets(self, targets):
+        """The labels training accuracy is taken against: under mixing, per sample the target that carried the larger weight in
+        the last step (its own at lam >= 0.5, its partner's below); ``targets`` itself otherwise."""
+        plan = self.last_plan
+        if plan is None or plan.identity or plan.lam >= 0.5:
+            return targets
+        return self._partner_targets
+
+    def _mixed(self, inputs, targets):
+        """-> (the batch the model sees, loss function of its outputs) under this step's plan."""
+        mixer = self.mixer
+        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        plan = mixer.plan(inputs.shape[0], inputs.shape[-2], inputs.shape[-1], self._epoch, self._step, rank)
+        self._step += 1
+        self.last_plan = plan
+        if plan.identity:
+            self._partner_targets = targets
+            return inputs, lambda out: ops.soft_cross_entropy(out, targets, None, None, mixer.label_smoothing)
+        inputs = ops.clip_mix(inputs, plan.partner, plan.mode, plan.lam, plan.box)
+        # the partner permutation travels pinned and asynchronously, as the blend's table does: no host read, no sync
+        perm = torch.tensor(plan.partner, dtype=torch.int64).pin_memory().to(targets.device, non_blocking=True)
+        tb = self._partner_targets = targets[perm]
+        lam = torch.full((inputs.shape[0],), plan.lam, dtype=torch.float32, device=targets.device)
+        return inputs, lambda out: ops.soft_cross_entropy(out, targets, tb, lam, mixer.label_smoothing)
 
     def __call__(self, inputs, targets):
         if self._flat:
             sync_buffers(self.model)
+        loss_fn = None
+        if self.mixer is not None:
+            inputs, loss_fn = self._mixed(inputs, targets)
         sync_ctx = self.model.no_sync() if self._flat else contextlib.nullcontext()
         with sync_ctx:
             outputs = self.model(inputs, o_type=self.task)
-            loss = self._ce(outputs, targets)
+            loss = self._ce(outputs, targets) if loss_fn is None else loss_fn(outputs)
             self.optimizer.zero_grad()
             loss.backward()
         if self._flat:

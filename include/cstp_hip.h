@@ -327,6 +327,19 @@ int cstp_cross_entropy_forward(void* stream, const float* logits, const int64_t*
                                int32_t k);
 int cstp_cross_entropy_backward(void* stream, const float* logits, const int64_t* labels, const float* dloss,
                                 float* dlogits, int32_t b, int32_t k);
+/* Soft-target cross-entropy (mean) for fine-tuning with label smoothing and mixup / CutMix: per row two targets ta[b], tb[b]
+ * (int64, device), a weight lam[b] (fp32, device) and one host scalar eps in [0, 1):
+ *   q[r][c] = (1-eps)*(lam[r]*[c==ta[r]] + (1-lam[r])*[c==tb[r]]) + eps/k
+ *   loss[0] = mean_r -sum_c q[r][c]*log_softmax(logits[r])[c]           (= F.cross_entropy(logits, q); with lam = 1 it is
+ *                                                                          F.cross_entropy(logits, ta, label_smoothing=eps))
+ *   backward: dlogits = dloss[0] * (softmax - q) / b.
+ * tb == NULL means tb = ta and lam == NULL means lam = 1 (smoothing only).  A target outside [0, k) contributes no one-hot mass
+ * and is never used as an index (the backward stays the gradient of that loss: softmax is weighted by the row's sum of q).  One wave per row with the lanes along k, the batch mean accumulated in double, fixed-order
+ * reductions and no atomics: equal inputs give equal bits.  b*k < 2^31; dlogits must not alias logits. */
+int cstp_soft_cross_entropy_forward(void* stream, const float* logits, const int64_t* ta, const int64_t* tb, const float* lam,
+                                    float eps, float* loss, int32_t b, int32_t k);
+int cstp_soft_cross_entropy_backward(void* stream, const float* logits, const int64_t* ta, const int64_t* tb, const float* lam,
+                                     float eps, const float* dloss, float* dlogits, int32_t b, int32_t k);
 /* NT-Xent loss/NTXent.py:46-62 on reps = cat(zjs, zis) [2n][f] (cosine similarity, eps 1e-8).
  * forward needs ws of cstp_ntxent_workspace_bytes (the 2n x 2n similarity matrix + norms);
  * backward reuses that ws and writes dreps [2n][f]. */
@@ -418,6 +431,26 @@ size_t cstp_clip_batch_desc_bytes(void);
 int cstp_clip_batch_forward(void* stream, const cstp_clip_batch_desc* desc_dev, const cstp_clip_batch_desc* desc_host, int32_t n,
                             int32_t t, int32_t size, const int32_t* frame_idx, int32_t n_idx, uint8_t* tmp, int64_t tmp_pixels,
                             float* out, int32_t out_slots, uint8_t* out8, int32_t out8_slots);
+
+/* ---- mixup / CutMix of a batch of fp32 clips (fine-tuning; no reference counterpart) ----
+ * x: [b][planes][h][w] (planes = 3*T) -> y of the same shape, y must not alias x.  One launch, driven by a DEVICE table with one
+ * entry per sample i:
+ *   mode 0: y[i] = x[i]
+ *   mode 1: y[i] = lam*x[i] + (1-lam)*x[partner]                                   (mixup)
+ *   mode 2: y[i] = x[partner] inside the half-open box [y0,y1) x [x0,x1) of every plane, x[i] outside: bits are copied (CutMix)
+ * 16-byte accesses when w % 4 == 0 and both bases are 16-byte aligned, scalar ones otherwise.  Every block checks the entry it
+ * uses (partner in [0, b), mode 1 / 2, 0 <= y0 <= y1 <= h, 0 <= x0 <= x1 <= w); a malformed entry, and a sample that is its own
+ * partner, is served as mode 0 instead of being followed.  b <= 65535, b*planes*h*w < 2^31.  No backward: clips carry no
+ * gradient. */
+typedef struct cstp_clip_mix_entry {
+  int32_t partner;         /* row of the batch this sample is blended with */
+  int32_t mode;            /* 0 copy, 1 mixup, 2 CutMix */
+  float lam;               /* blend weight of the sample itself (mixup) */
+  int32_t y0, y1, x0, x1;  /* CutMix box, the same in every plane */
+  int32_t reserved;        /* pads the entry to 32 bytes */
+} cstp_clip_mix_entry;
+int cstp_clip_mix(void* stream, const float* x, float* y, const cstp_clip_mix_entry* table, int32_t b, int32_t planes, int32_t h,
+                  int32_t w);
 
 /* ---- per-step utilities over FLAT parameter arenas -------------------------------------- */
 /* EMA r21d_byol.py:331-337: target = target*m + online*(1-m) over n floats. */

@@ -23,6 +23,9 @@ What differs (each a fix of something that cannot work in the reference, none ch
     (cstp_amd.sampler + cstp_clip_batch_forward: a whole batch in two launches) in place of the PIL worker pipeline;
     --dataset UcfFineTune feeds the same path from UCF-style frame folders (--frame_dir, --annotation_path, --split;
     --n_workers JPEG decode threads; cstp_amd.frame_folder).
+What is added (off by default, then the step is the one above): --label_smoothing, --mixup_alpha, --cutmix_alpha, --mix_prob,
+--mix_switch_prob regularise TRAINING with smoothed / mixed targets and blended clips (cstp_amd.mix, cstp_clip_mix,
+cstp_soft_cross_entropy_*); training accuracy is then taken against the target that carried the larger weight.
 """
 from __future__ import annotations
 
@@ -36,6 +39,7 @@ import torch
 import torch.distributed as dist
 
 from cstp_amd import ops
+from cstp_amd.mix import build_mixer
 from cstp_amd.model import generate_model
 from cstp_amd.optim import build_optimizer
 from cstp_amd.opts import parse_opts
@@ -107,7 +111,7 @@ def train(epoch, train_dataloader, step_fn, optimizer, opts, train_logger, len_t
         i += 1
         data_time.update(time.time() - end_time)
         loss, outputs = step_fn(inputs, targets)
-        acc = calculate_accuracy(outputs, targets)
+        acc = calculate_accuracy(outputs, step_fn.accuracy_targets(targets))   # under mixing: the heavier target
         reduced_loss = reduce_mean(loss, opts.world_size)
         losses.update(reduced_loss.item(), inputs.size(0))
         accuracies.update(acc, inputs.size(0))
@@ -226,13 +230,16 @@ def main_worker(local_rank, opts):
     if resume:
         optimizer.load_state_dict(torch.load(opts.resume_md_path, map_location=torch.device("cuda", local_rank))["optimizer"])
     scheduler = ReduceLROnPlateau(optimizer, "min", patience=opts.lr_patience)
-    step_fn = FineTuneStep(model, optimizer, o_type_for(opts.task))
+    # --label_smoothing / --mixup_alpha / --cutmix_alpha (all tasks served here); None at the defaults.  Training only:
+    # validation below keeps the plain cross-entropy, so the plateau scheduler's metric stays comparable between runs
+    step_fn = FineTuneStep(model, optimizer, o_type_for(opts.task), mixer=build_mixer(opts))
 
     for epoch in range(begin_epoch, opts.n_epochs + 1):
         print("Start to fine-tune")
         print("Start training epoch {}".format(epoch))
         if train_sampler is not None:
             train_sampler.set_epoch(epoch)
+        step_fn.set_epoch(epoch)
         train(epoch, train_dataloader, step_fn, optimizer, opts, train_logger, len_train_data)
         print("Start validating epoch {}".format(epoch))
         validation(epoch, val_dataloader, model, optimizer, opts, val_logger, len_val_data, scheduler)
