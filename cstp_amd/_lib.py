@@ -191,6 +191,8 @@ SIGNATURES = {
     # retrieval: streaming similarity top-k (csrc/retrieve.hip)
     "cstp_simtopk_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
     "cstp_simtopk": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, c_size_t]),
+    # k-NN classification: the weighted vote on a top-k list (csrc/retrieve.hip)
+    "cstp_knn_vote": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_float, c_int32, _P, _P]),
 }
 
 _lib = None

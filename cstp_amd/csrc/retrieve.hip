@@ -22,6 +22,12 @@
 // same insertion in split order.  The k best under a total order are unique, so the answer does not depend on nsplit.
 // No atomics of any kind: two calls give the same bits.  Every global index is formed from a row < nq / < ng and a feature
 // < d that were checked first; masked elements are zeros (fmaf(0, 0, acc) leaves acc as it is).
+//
+// knn_vote_kernel: the weighted k-nearest-neighbour vote on such lists (include/cstp_hip.h: cstp_knn_vote).  One wave per
+// query, four per block, lane j = slot j.  A lane's class sum is a k-step loop over the slots (readlane of the slot's label and
+// weight, added where the label is the lane's own): slot order, so every slot of a class holds the same bits, and no class
+// table in LDS or memory -- the number of classes is unbounded.  The first slot of a class represents it; the n_top answers are
+// n_top wave-wide arg-max rounds over the representatives by (score descending, class ascending).
 #include <math.h>
 #include <stdlib.h>
 
@@ -225,6 +231,62 @@ simtopk_merge_kernel(const float* __restrict__ pv, const int* __restrict__ pi, i
   }
 }
 
+constexpr int KV_MAX_TOP = 8;
+
+// one wave per query: val / idx [nq][k] as simtopk writes them -> the n_top best classes of the weighted vote
+__global__ void __launch_bounds__(256)
+knn_vote_kernel(const float* __restrict__ val, const int* __restrict__ idx, const int* __restrict__ g_labels, int nq, int ng,
+                int k, float inv_t, int n_top, int* __restrict__ pred, float* __restrict__ score) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= nq) return;                                                  // wave-uniform
+  float v = -INFINITY;
+  int j = -1;
+  if (lane < k) {
+    v = val[(size_t)row * k + lane];
+    j = idx[(size_t)row * k + lane];
+  }
+  const bool live = j >= 0 && j < ng;                                     // lanes >= k kept j = -1
+  const int lab = live ? g_labels[j] : -1;                                // a dead slot's idx never forms an address
+  const float v0 = lane_f(v, 0);                                          // the row's largest value: w_0 = 1, no overflow
+  const float w = live ? expf((v - v0) * inv_t) : 0.f;
+  float sum = 0.f;
+  bool rep = live;                                                        // the first slot of a class stands for it
+  for (int s = 0; s < k; ++s) {
+    const int ls = __builtin_amdgcn_readlane(lab, s);
+    const float ws = lane_f(w, s);
+    if (ls == lab) {
+      sum += ws;                                                          // s ascending: one order for every slot of the class
+      if (s < lane) rep = false;
+    }
+  }
+  int out_c = -1;
+  float out_s = 0.f;
+  for (int r = 0; r < n_top; ++r) {
+    float bs = rep ? sum : -1.f;                                          // scores are >= 0: -1 is "no candidate"
+    int bc = rep ? lab : 0x7fffffff;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const float os = __shfl_xor(bs, off, 64);
+      const int oc = __shfl_xor(bc, off, 64);
+      if (os > bs || (os == bs && oc < bc)) {
+        bs = os;
+        bc = oc;
+      }
+    }
+    if (bs < 0.f) break;                                                  // wave-uniform: the distinct classes ran out
+    if (lane == r) {
+      out_c = bc;
+      out_s = bs;
+    }
+    if (rep && lab == bc) rep = false;
+  }
+  if (lane < n_top) {
+    pred[(size_t)row * n_top + lane] = out_c;
+    score[(size_t)row * n_top + lane] = out_s;
+  }
+}
+
 inline bool shape_ok(int nq, int ng, int d, int k) {
   return nq >= 1 && ng >= 1 && d >= 1 && k >= 1 && k <= SQ_MAX_K && (long)ng + SQ_TG < (1L << 31) &&
          (long)nq + SQ_TQ < (1L << 31);
@@ -282,5 +344,19 @@ extern "C" int cstp_simtopk(void* stream, const float* q, const float* g, int32_
     hipLaunchKernelGGL(simtopk_merge_kernel, dim3(cdiv(nq, 4)), dim3(256), 0, st, pv, pi, nq, k, ns, val, idx);
     CSTP_LAUNCH_CHECK();
   }
+  return 0;
+}
+
+extern "C" int cstp_knn_vote(void* stream, const float* val, const int32_t* idx, const int32_t* g_labels, int32_t nq, int32_t ng,
+                             int32_t k, float inv_t, int32_t n_top, int32_t* pred, float* score) {
+  CSTP_REQUIRE(val != nullptr && idx != nullptr && g_labels != nullptr && pred != nullptr && score != nullptr, "null argument");
+  CSTP_REQUIRE(nq >= 1 && ng >= 1, "bad shape");
+  CSTP_REQUIRE(k >= 1 && k <= SQ_MAX_K, "k must be in 1..64");
+  CSTP_REQUIRE(n_top >= 1 && n_top <= KV_MAX_TOP, "n_top must be in 1..8");
+  CSTP_REQUIRE(isfinite(inv_t) && inv_t > 0.f, "inv_t must be finite and positive");
+  const unsigned blocks = (unsigned)(((long)nq + 3) / 4);
+  hipLaunchKernelGGL(knn_vote_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), val, idx, g_labels, nq, ng, k, inv_t, n_top,
+                     pred, score);
+  CSTP_LAUNCH_CHECK();
   return 0;
 }

@@ -1859,6 +1859,52 @@ def sim_topk(q, g, k, exclude_self=False):
     return val, idx
 
 
+KNN_VOTE_MAX_TOP = 8
+
+
+def knn_vote(val, idx, g_labels, temperature, n_top=5):
+    """The weighted k-nearest-neighbour vote on a sim_topk answer (val [nq, k] fp32, idx [nq, k] int32) with the gallery's class
+    ids g_labels [ng] (int64 or int32, >= 0): slot j weighs exp((val_j - val_0) / temperature), a class scores the sum of its
+    slots' weights in slot order, -> (pred [nq, n_top] int32, score [nq, n_top] fp32): the n_top best distinct classes by
+    (score descending, class id ascending), (-1, 0) where they run out.  Slots with idx outside 0..ng-1 are dead.
+    One launch, no class table, no atomics (include/cstp_hip.h: cstp_knn_vote).  No autograd."""
+    if val.dim() != 2 or idx.dim() != 2 or val.shape != idx.shape:
+        raise _lib.CstpError("knn_vote expects val and idx of one shape [queries, k], got %s and %s"
+                             % (tuple(val.shape), tuple(idx.shape)))
+    if g_labels.dim() != 1:
+        raise _lib.CstpError("knn_vote: gallery labels must be [gallery rows], got %s" % (tuple(g_labels.shape),))
+    if val.dtype != torch.float32:
+        raise _lib.CstpError("knn_vote val must be float32, got %s" % (val.dtype,))
+    if idx.dtype != torch.int32:
+        raise _lib.CstpError("knn_vote idx must be int32, got %s" % (idx.dtype,))
+    if g_labels.dtype not in (torch.int64, torch.int32):
+        raise _lib.CstpError("knn_vote gallery labels must be int64 or int32, got %s" % (g_labels.dtype,))
+    if isinstance(n_top, bool) or not isinstance(n_top, int) or not 1 <= n_top <= KNN_VOTE_MAX_TOP:
+        raise _lib.CstpError("knn_vote: n_top must be an int in 1..%d, got %r" % (KNN_VOTE_MAX_TOP, n_top))
+    temperature = float(temperature)
+    if not (temperature > 0.0 and temperature < float("inf")):
+        raise _lib.CstpError("knn_vote: temperature must be finite and positive, got %r" % (temperature,))
+    nq, k = val.shape
+    ng = g_labels.shape[0]
+    if not 1 <= k <= SIM_TOPK_MAX_K:
+        raise _lib.CstpError("knn_vote: k must be in 1..%d, got %d" % (SIM_TOPK_MAX_K, k))
+    if nq < 1 or ng < 1:
+        raise _lib.CstpError("knn_vote: empty operand, %d queries and %d gallery labels" % (nq, ng))
+    for t, name in ((val, "knn_vote val"), (idx, "knn_vote idx"), (g_labels, "knn_vote gallery labels")):
+        if not t.is_cuda:
+            raise _lib.CstpError("%s must be on a HIP device (cstp_amd has no CPU path)" % name)
+    if not (val.device == idx.device == g_labels.device):
+        raise _lib.CstpError("knn_vote: val on %s, idx on %s, gallery labels on %s" % (val.device, idx.device, g_labels.device))
+    lib = _lib.load()
+    val, idx = val.detach().contiguous(), idx.contiguous()
+    labels = g_labels.to(torch.int32).contiguous()                   # the one conversion
+    pred = torch.empty((nq, n_top), dtype=torch.int32, device=val.device)
+    score = torch.empty((nq, n_top), dtype=torch.float32, device=val.device)
+    check(lib.cstp_knn_vote(_stream(), val.data_ptr(), idx.data_ptr(), labels.data_ptr(), nq, ng, k, 1.0 / temperature, n_top,
+                            pred.data_ptr(), score.data_ptr()), "cstp_knn_vote")
+    return pred, score
+
+
 # ----------------------------------------------------------------------------------------------
 # flat-arena utilities (no autograd)
 # ----------------------------------------------------------------------------------------------

@@ -21,6 +21,11 @@ Additions (all optional, defaults reproduce the reference):
   --mix_switch_prob  fine-tuning: probability of CutMix when both alphas are positive (default 0.5)
                      (cstp_amd/mix.py; validation keeps the plain cross-entropy; main_byol.py, test.py and retrieval.py
                      ignore all five)
+  --knn_k           weighted k-NN classification (knn.py, the --knn_every monitor): neighbours per query, 1..64 (default 20)
+  --knn_t           its temperature: neighbour j weighs exp((sim_j - sim_0) / T), must be > 0 (default 0.07)
+  --knn_every       main_byol.py: after every E-th epoch and after the last, rank 0 classifies the labelled test videos by k-NN
+                    on the online encoder and logs top-1 in the ``acc`` column (default 0 = off); --dataset synthetic_video and
+                    UcfRepreBYOLSpPre, --sample_size 112 | 224 (main_ft_mp.py, test.py and retrieval.py ignore all three)
 torchrun passes LOCAL_RANK through the environment instead of --local_rank; both are honoured.
 """
 from __future__ import annotations
@@ -114,6 +119,7 @@ _FLAGS = [
     ("cutmix_alpha", 0.0, float, "main_ft_mp.py: CutMix, lam ~ Beta(alpha, alpha) once per batch, one box through all frames (0 = off)"),
     ("mix_prob", 1.0, float, "main_ft_mp.py: probability that a batch is mixed (with --mixup_alpha / --cutmix_alpha)"),
     ("mix_switch_prob", 0.5, float, "main_ft_mp.py: probability of CutMix instead of mixup when both alphas are positive"),
+    ("knn_every", 0, int, "main_byol.py: k-NN top-1 of the online encoder after every E-th epoch and after the last (0 = off)"),
 ]
 RETRIEVAL_MAX_K = 64      # ops.SIM_TOPK_MAX_K: one lane per list slot
 
@@ -123,6 +129,20 @@ def _retrieval_k(text):
     if not 1 <= k <= RETRIEVAL_MAX_K:
         raise argparse.ArgumentTypeError("--retrieval_k takes values in 1..%d, got %d" % (RETRIEVAL_MAX_K, k))
     return k
+
+
+def _knn_k(text):
+    k = int(text)
+    if not 1 <= k <= RETRIEVAL_MAX_K:
+        raise argparse.ArgumentTypeError("--knn_k takes values in 1..%d, got %d" % (RETRIEVAL_MAX_K, k))
+    return k
+
+
+def _knn_t(text):
+    t = float(text)
+    if not (t > 0.0 and t < float("inf")):
+        raise argparse.ArgumentTypeError("--knn_t must be finite and > 0, got %r" % (text,))
+    return t
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -138,6 +158,9 @@ def build_parser() -> argparse.ArgumentParser:
                         help="weights of (byol, spatial overlap, temporal overlap, playback rate, rotation)")
     parser.add_argument("--retrieval_k", default=[1, 5, 10, 20, 50], nargs="+", type=_retrieval_k,
                         help="retrieval.py: the k of R@k, each in 1..%d" % RETRIEVAL_MAX_K)
+    parser.add_argument("--knn_k", default=20, type=_knn_k,
+                        help="knn.py / --knn_every: neighbours per query, 1..%d" % RETRIEVAL_MAX_K)
+    parser.add_argument("--knn_t", default=0.07, type=_knn_t, help="knn.py / --knn_every: temperature of the vote, > 0")
     return parser
 
 

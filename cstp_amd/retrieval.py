@@ -19,6 +19,41 @@ def _inner(model):
     return model.module if hasattr(model, "module") and not hasattr(model, "encode") else model
 
 
+def build_video_sets(opts, dataset=None, what="retrieval"):
+    """-> (gallery loader, query loader): one whole video per item, as the video test reads them; the train list is the gallery,
+    the test list the queries.  ``dataset`` None: opts.dataset under --transform_mode img_test (the retrieval.py / knn.py
+    drivers); named ("synthetic_video" | "UcfFineTune"): that kind of set from the same flags, whatever opts.dataset and
+    opts.transform_mode say (the k-NN monitor of main_byol.py, whose own data set is the unlabelled pre-training one)."""
+    if dataset is None:
+        if opts.transform_mode != "img_test":
+            raise ValueError("%s reads whole videos: --transform_mode img_test, got %r" % (what, opts.transform_mode,))
+        dataset = opts.dataset
+    if dataset == "synthetic_video":
+        from .clip_ops import GpuLabelledLoader, GpuLabelledVideos
+        kw = dict(n_classes=opts.n_classes, sample_duration=opts.sample_duration, sample_size=opts.sample_size,
+                  pb_rate=opts.pb_rate)
+        # two instances: other noise, other lengths, the same class-dependent patterns
+        gallery = GpuLabelledVideos(opts.device, "test", "img_test", n_videos=max(opts.retrieval_gallery_len, 1),
+                                    seed=opts.manual_seed + 1, **kw)
+        queries = GpuLabelledVideos(opts.device, "test", "img_test", n_videos=max(opts.synthetic_len // 4, 1),
+                                    seed=opts.manual_seed, **kw)
+        return GpuLabelledLoader(gallery), GpuLabelledLoader(queries)
+    if dataset == "UcfFineTune":
+        from .frame_folder import FrameLabelledLoader, build_finetune
+        gallery = build_finetune(opts, opts.device, "test", "img_test", list_from="train")
+        queries = build_finetune(opts, opts.device, "test", "img_test")
+        return FrameLabelledLoader(gallery), FrameLabelledLoader(queries)
+    raise NotImplementedError("dataset %r: %s serves --dataset synthetic_video and UcfFineTune" % (dataset, what))
+
+
+def close_video_sets(*loaders) -> None:
+    """Stops the decode threads of frame-folder loaders (the synthetic ones have none)."""
+    for loader in loaders:
+        close = getattr(loader.dataset, "close", None)
+        if close is not None:
+            close()
+
+
 def extract_features(model, loader) -> Tuple[torch.Tensor, torch.Tensor]:
     """``loader`` yields one video per item as the video-test loaders do: (clips [1, n_clips, 3, T, S, S], label [1]).
     -> (features [n, d] fp32, labels [n] int64) on the device of the clips; row v is the mean of encode() over video v's clips.

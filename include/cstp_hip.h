@@ -652,6 +652,21 @@ size_t cstp_simtopk_workspace_bytes(int32_t nq, int32_t ng, int32_t d, int32_t k
 int cstp_simtopk(void* stream, const float* q, const float* g, int32_t nq, int32_t ng, int32_t d, int32_t k,
                  int32_t exclude_self, float* val, int32_t* idx, void* ws, size_t ws_bytes);
 
+/* ---- weighted k-nearest-neighbour classification: the vote on a similarity top-k list (csrc/retrieve.hip) ------------------
+ * val / idx [nq][k] are exactly what cstp_simtopk writes: similarity descending, (-inf, -1) where candidates ran out.
+ * g_labels [ng] int32, values >= 0.  pred / score [nq][n_top].  Per row:
+ *   slot j is LIVE iff 0 <= idx[j] < ng; a dead slot weighs 0 and its idx is never used to form an address;
+ *   w_j = expf((val_j - val_0) * inv_t) in fp32, val_0 the row's first (largest) value: w_0 = 1 and nothing overflows at any
+ *         temperature, whether or not the features were normalised;
+ *   score(c) = sum of w_j over the live slots with g_labels[idx_j] == c, added in slot order j ascending (one fixed order: no
+ *         atomics, no class table, so the number of classes is unbounded, and two slots of one class see the same bits);
+ *   output: the n_top best distinct classes by (score descending, class id ascending); (-1, 0.0f) where they run out.
+ * Equal inputs give equal bits on every call.  One launch, one wave per query, no workspace.
+ * Limits: 1 <= k <= 64, 1 <= n_top <= 8, nq >= 1, ng >= 1, inv_t finite and > 0, no null pointer; anything else is refused
+ * before any HIP call. */
+int cstp_knn_vote(void* stream, const float* val, const int32_t* idx, const int32_t* g_labels, int32_t nq, int32_t ng,
+                  int32_t k, float inv_t, int32_t n_top, int32_t* pred, float* score);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,9 +20,13 @@ uint8 videos in HBM and samples / rotates / crops / resizes / flips / normalises
 reads UCF-style frame folders (--frame_dir, --annotation_path, --split; --n_workers decode threads) and runs everything
 after the JPEG decode on the GPU (cstp_amd.frame_folder); the LMDB data sets are out of scope; the log scalars reach the host through one pinned-memory copy per iteration, read one step late
 (cstp_amd.train.LaggedScalars), instead of seven .item() syncs and a blocking all-reduce per iteration.
+New: --knn_every E (default 0 = off) fills the ``acc`` column of the epoch log, which the reference leaves empty: after every E-th
+epoch and after the last one rank 0 classifies labelled test videos by weighted k-NN on the ONLINE encoder (cstp_amd.knn, --knn_k,
+--knn_t) under model.eval() + no_grad, the other ranks wait in a barrier, and training goes on unchanged (KnnMonitor).
 """
 from __future__ import annotations
 
+import argparse
 import builtins
 import os
 import random
@@ -34,6 +38,7 @@ import torch.distributed as dist
 from torch.utils.data import DataLoader
 from torch.utils.data.distributed import DistributedSampler
 
+from cstp_amd import knn, retrieval, sampler as clip_sampler
 from cstp_amd.model import generate_model
 from cstp_amd.ntxent import NTXentLoss
 from cstp_amd.optim import build_optimizer
@@ -60,7 +65,63 @@ def build_dataset(opts):
     return SyntheticClips(opts.synthetic_len, opts.sample_duration, opts.sample_size, opts.manual_seed)
 
 
-def train_BYOL(epoch, loader, step_fn, optimizer, opts, train_logger):
+def check_knn_opts(opts):
+    """Refuses what the --knn_every monitor cannot serve; called before any device work.  0 = off: nothing to check."""
+    every = getattr(opts, "knn_every", 0)
+    if every < 0:
+        raise ValueError("--knn_every takes 0 (off) or a positive number of epochs, got %d" % every)
+    if every == 0:
+        return
+    if opts.dataset not in KnnMonitor.SETS:
+        raise ValueError("--knn_every %d with --dataset %s: the k-NN monitor needs labelled videos, which --dataset "
+                         "synthetic_video and UcfRepreBYOLSpPre have (--dataset synthetic is unlabelled random clips)"
+                         % (every, opts.dataset))
+    try:
+        clip_sampler.short_side(opts.sample_size)
+    except ValueError:
+        raise ValueError("--knn_every %d with --sample_size %d: the monitor reads whole videos as the video test does, and its "
+                         "ClipScale serves --sample_size 112 and 224 only" % (every, opts.sample_size)) from None
+
+
+class KnnMonitor:
+    """--knn_every: ``monitor(epoch)`` -> the k-NN top-1 of the online encoder after every E-th epoch and after the last, else
+    None.  Rank 0 evaluates (cstp_amd.knn.evaluate: eval mode, no_grad, the mode restored) and prints; under DDP every rank then
+    meets in a barrier, so the evaluation has to finish inside the collective timeout.  The evaluation draws from no random
+    generator and updates no buffer: the training that follows is the training without it."""
+
+    # the pre-training data set -> the labelled whole-video sets of the same flags (retrieval.build_video_sets)
+    SETS = {"synthetic_video": "synthetic_video", "UcfRepreBYOLSpPre": "UcfFineTune"}
+
+    def __init__(self, opts, model, local_rank):
+        check_knn_opts(opts)
+        self.every, self.last, self.k, self.t = opts.knn_every, opts.n_epochs, opts.knn_k, opts.knn_t
+        self.model, self.distributed, self.loaders = model, opts.distributed, None
+        if max(opts.rank, 0) == 0:
+            sets_opts = argparse.Namespace(**vars(opts))
+            sets_opts.device = torch.device("cuda", local_rank)
+            self.loaders = retrieval.build_video_sets(sets_opts, self.SETS[opts.dataset])
+            print("kNN monitor: {} gallery videos, {} query videos, k = {}, T = {}".format(
+                len(self.loaders[0]), len(self.loaders[1]), self.k, self.t))
+
+    def __call__(self, epoch):
+        if epoch % self.every != 0 and epoch != self.last:
+            return None
+        top1 = None
+        if self.loaders is not None:
+            res = knn.evaluate(self.model, self.loaders[0], self.loaders[1], self.k, self.t)
+            print("Epoch {}: kNN top-1 = {:.4f}".format(epoch, res["top1"]))
+            print("Epoch {}: kNN top-5 = {:.4f}".format(epoch, res["top5"]))
+            top1 = res["top1"]
+        if self.distributed:
+            dist.barrier()
+        return top1
+
+    def close(self):
+        if self.loaders is not None:
+            retrieval.close_video_sets(*self.loaders)
+
+
+def train_BYOL(epoch, loader, step_fn, optimizer, opts, train_logger, knn_monitor=None):
     meters = {k: AverageMeter() for k in ("batch", "data", "loss", "loss_byol", "loss_pred_spa", "loss_pred_tem",
                                           "loss_pred_pb", "loss_pred_rot")}
     dev = torch.device("cuda", opts.local_rank)
@@ -102,9 +163,10 @@ def train_BYOL(epoch, loader, step_fn, optimizer, opts, train_logger):
     last = lagged.flush()
     if last is not None:
         log_line(last)
+    acc = knn_monitor(epoch) if knn_monitor is not None else None      # every rank calls it: it ends in a barrier under DDP
     if opts.local_rank == 0:
         row = {k: meters[k].avg for k in LOG_COLUMNS if k in meters}
-        row.update({"epoch": epoch, "acc": None, "lr": float("{:.5f}".format(optimizer.param_groups[-1]["lr"]))})
+        row.update({"epoch": epoch, "acc": acc, "lr": float("{:.5f}".format(optimizer.param_groups[-1]["lr"]))})
         train_logger.log(row)
         if opts.rank == 0 and epoch % 100 == 0:     # rank 0 writes its own state: what DDP's broadcast hands every rank
             path = os.path.join(opts.result_path, opts.dataset, opts.task, "save_{}.pth".format(epoch))
@@ -174,6 +236,7 @@ def main_worker(local_rank, opts):
         scheduler.step()
     step_fn = PretrainStep(model, optimizer, opts.loss_weight, task=opts.task, clip_grad_norm=opts.clip_grad_norm,
                            ntxent=criterion_ctr, ntxent_weight=opts.ntxent_weight)
+    knn_monitor = KnnMonitor(opts, model, local_rank) if getattr(opts, "knn_every", 0) > 0 else None
     if opts.task in ("r_byol", "loss_com"):
         print("Start to train BYOL CoCLR data augmentation pre-trained model!")
         for epoch in range(begin_epoch, opts.n_epochs + 1):
@@ -181,14 +244,17 @@ def main_worker(local_rank, opts):
             if sampler is not None:
                 sampler.set_epoch(epoch)
             model.train()
-            train_BYOL(epoch, loader, step_fn, optimizer, opts, train_logger)
+            train_BYOL(epoch, loader, step_fn, optimizer, opts, train_logger, knn_monitor)
             scheduler.step()
+    if knn_monitor is not None:
+        knn_monitor.close()
     if opts.distributed:
         dist.barrier()
         dist.destroy_process_group()
 
 
 def main(opts):
+    check_knn_opts(opts)
     torch.manual_seed(opts.manual_seed)
     np.random.seed(opts.manual_seed)
     random.seed(opts.manual_seed)

@@ -27,24 +27,7 @@ from cstp_amd.opts import parse_opts
 
 def build_sets(opts):
     """-> (gallery loader, query loader): one whole video per item, as the video test reads them."""
-    if opts.transform_mode != "img_test":
-        raise ValueError("retrieval reads whole videos: --transform_mode img_test, got %r" % (opts.transform_mode,))
-    if opts.dataset == "synthetic_video":
-        from cstp_amd.clip_ops import GpuLabelledLoader, GpuLabelledVideos
-        kw = dict(n_classes=opts.n_classes, sample_duration=opts.sample_duration, sample_size=opts.sample_size,
-                  pb_rate=opts.pb_rate)
-        # two instances: other noise, other lengths, the same class-dependent patterns
-        gallery = GpuLabelledVideos(opts.device, "test", "img_test", n_videos=max(opts.retrieval_gallery_len, 1),
-                                    seed=opts.manual_seed + 1, **kw)
-        queries = GpuLabelledVideos(opts.device, "test", "img_test", n_videos=max(opts.synthetic_len // 4, 1),
-                                    seed=opts.manual_seed, **kw)
-        return GpuLabelledLoader(gallery), GpuLabelledLoader(queries)
-    if opts.dataset == "UcfFineTune":
-        from cstp_amd.frame_folder import FrameLabelledLoader, build_finetune
-        gallery = build_finetune(opts, opts.device, "test", "img_test", list_from="train")
-        queries = build_finetune(opts, opts.device, "test", "img_test")
-        return FrameLabelledLoader(gallery), FrameLabelledLoader(queries)
-    raise NotImplementedError("dataset %r: retrieval serves --dataset synthetic_video and UcfFineTune" % opts.dataset)
+    return retrieval.build_video_sets(opts)
 
 
 def run(opts):
