@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_uint32, POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import c_uint32, c_uint64, POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # CSTP_LIB_PATH: developer override for A/B-ing kernel builds (tools/ab_*.sh); unset in production
@@ -193,6 +193,11 @@ SIGNATURES = {
     "cstp_simtopk": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, c_size_t]),
     # k-NN classification: the weighted vote on a top-k list (csrc/retrieve.hip)
     "cstp_knn_vote": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_float, c_int32, _P, _P]),
+    # fine-tuning regularisers: dropout and the stochastic-depth residual join (csrc/reg.h)
+    "cstp_philox4x32_10": (c_int32, [POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32)]),
+    "cstp_dropout": (c_int32, [_P, _P, _P, c_int64, c_float, c_uint64, c_uint64]),
+    "cstp_droppath_add_relu_forward": (c_int32, [_P, _P, _P, _P, _P, c_int64, c_int64, c_int32, _P]),
+    "cstp_droppath_add_relu_backward": (c_int32, [_P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int32]),
 }
 
 _lib = None

@@ -660,3 +660,4 @@ extern "C" int cstp_maxpool3d_backward(void* stream, const float* dy, const int3
 }
 
 #include "lars.h"
+#include "reg.h"

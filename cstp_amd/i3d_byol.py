@@ -205,15 +205,19 @@ class AvgPool3d(nn.Module):
 
 
 class Dropout(nn.Module):
-    """nn.Dropout(p) stand-in (no state); I3DBYOL builds it with p = 0, the identity."""
+    """nn.Dropout(p) stand-in (no state); I3DBYOL builds it with p = 0, the identity.  --dropout sets ``p`` and the step's mask
+    ``key`` for one training forward (I3DBYOL.regularized): the mask is the counter-based one of ops.dropout, not torch's."""
 
     def __init__(self, p=0.0):
         super().__init__()
         if p != 0:
-            raise NotImplementedError("I3D's classifier dropout is built with p = 0 (i3d_byol.py:227,630); p = %r has no kernel" % (p,))
-        self.p = p
+            raise NotImplementedError("I3D's classifier dropout is built with p = 0 (i3d_byol.py:227,630); a positive p comes "
+                                      "from --dropout per training step, not from the constructor (got %r)" % (p,))
+        self.p, self.key = p, None
 
     def forward(self, x):
+        if self.training and self.p > 0 and self.key is not None:
+            return ops.dropout(x, self.p, self.key, 0)
         return x
 
 
@@ -331,6 +335,13 @@ class I3DBYOL(ByolBase):
     def _head_bn_calls(self):
         return [(self.predictor, 2)]
 
+    def regularized(self, dropout=None, drop_scales=None):
+        """--dropout sets the probability (and this step's key) of the encoder's own ``dropout`` module, which sits in front of
+        conv3d_0c_1x1_custom; I3D has no residual blocks to drop."""
+        if drop_scales:
+            raise ValueError("--drop_path: i3d_byol has no residual branch to drop")
+        return _I3DDropout(self.online_net.dropout if not self.pretrain else None, dropout)
+
     def forward(self, x1, x2=None, o_type="r_byol"):
         if o_type == "loss_com":
             return self._two_view_step(x1, x2)
@@ -348,3 +359,20 @@ class I3DBYOL(ByolBase):
             raise AttributeError("I3DBYOL has no `classify`: o_type='scratch' fails in the reference too (i3d_byol.py:796-799); "
                                  "use o_type='ft_all'")
         return None     # the reference falls off the end of forward for any other o_type
+
+
+class _I3DDropout:
+    """I3DBYOL.regularized: (p, key) on the classifier's Dropout module for one forward, p = 0 again afterwards."""
+
+    def __init__(self, module, dropout):
+        self.module, self.dropout = module, dropout
+
+    def __enter__(self):
+        if self.module is not None and self.dropout is not None:
+            self.module.p, self.module.key = self.dropout
+        return self.module
+
+    def __exit__(self, *exc):
+        if self.module is not None:
+            self.module.p, self.module.key = 0, None
+        return False

@@ -1794,6 +1794,155 @@ def clip_mix(x, partner, mode, lam, boxes=None):
     return y
 
 
+# ----------------------------------------------------------------------------------------------
+# fine-tuning regularisers (csrc/reg.h, cstp_amd/regularize.py): dropout with a counter-based mask, the stochastic-depth join
+# ----------------------------------------------------------------------------------------------
+# A/B switch, read at import: 0 composes both operations from ATen calls on device tensors (the same mask, the same expression),
+# for comparison on one machine; the product path is the kernels.
+REG_FUSED = os.environ.get("CSTP_REG_FUSED", "1") != "0"
+_M32 = 0xFFFFFFFF
+
+
+def _mulhilo_aten(m: int, c: torch.Tensor):
+    """(hi, lo) 32-bit halves of m * c for int64 tensors holding values below 2^32: int64 products of 16 x 32 bits cannot wrap."""
+    a, b = (m >> 16) * c, (m & 0xFFFF) * c
+    t = ((a & 0xFFFF) << 16) + b
+    return (a >> 16) + (t >> 32), t & _M32
+
+
+def _dropout_keep_aten(n: int, p: float, key: int, offset: int, device) -> torch.Tensor:
+    """The keep mask of cstp_dropout for elements 0 .. n - 1 (bool [n]) from ATen integer arithmetic: CSTP_REG_FUSED=0 only."""
+    q = torch.arange((n + 3) // 4, dtype=torch.int64, device=device)
+    c = [q & _M32, q >> 32, torch.full_like(q, offset & _M32), torch.full_like(q, (offset >> 32) & _M32)]
+    k0, k1 = key & _M32, (key >> 32) & _M32
+    for _ in range(10):
+        hi0, lo0 = _mulhilo_aten(0xD2511F53, c[0])
+        hi1, lo1 = _mulhilo_aten(0xCD9E8D57, c[2])
+        c = [hi1 ^ c[1] ^ k0, lo1, hi0 ^ c[3] ^ k1, lo0]
+        k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
+    w = torch.stack(c, dim=1).reshape(-1)[:n]
+    u = (w >> 8).to(torch.float32) * float(2.0 ** -24)
+    return u >= torch.tensor(p, dtype=torch.float32, device=device)
+
+
+class _Dropout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, p, key, offset):
+        ctx.args = (p, key, offset)
+        return _Dropout._run(_req(x, "dropout input"), p, key, offset)
+
+    @staticmethod
+    def _run(x, p, key, offset):
+        y = torch.empty_like(x)
+        if x.numel():
+            check(_lib.load().cstp_dropout(_stream(), x.data_ptr(), y.data_ptr(), x.numel(), p, key, offset), "cstp_dropout")
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        return _Dropout._run(_req(dy, "dropout grad_output"), *ctx.args), None, None, None
+
+
+def dropout(x, p, key, offset=0):
+    """Inverted dropout with the counter-based mask of cstp_dropout: element e of the (contiguous) tensor is kept iff
+    Philox4x32-10((e >> 2, offset), key)[e & 3], as a 24-bit fraction, is >= p, and then scaled by 1 / (1 - p) in fp32.  ``key`` is the
+    step's uint64 (cstp_amd.regularize), ``offset`` numbers the call site.  The gradient is the same call on the incoming
+    gradient; no mask is stored.  p == 0 returns ``x`` itself."""
+    if not x.is_cuda:
+        raise _lib.CstpError("dropout input must be on a HIP device (cstp_amd has no CPU path)")
+    p = float(np.float32(p))
+    if not 0.0 <= p < 1.0:
+        raise _lib.CstpError("dropout p must lie in [0, 1), got %r" % (p,))
+    key, offset = int(key), int(offset)
+    if not (0 <= key < 2 ** 64 and 0 <= offset < 2 ** 64):
+        raise _lib.CstpError("dropout key and offset are unsigned 64-bit numbers, got %r, %r" % (key, offset))
+    if p == 0.0:
+        return x
+    if not REG_FUSED:
+        x = _req(x, "dropout input")
+        keep = _dropout_keep_aten(x.numel(), p, key, offset, x.device).view(x.shape)
+        inv = float(np.float32(1.0) / (np.float32(1.0) - np.float32(p)))             # the kernel's fp32 quotient
+        return torch.where(keep, x * inv, torch.zeros((), dtype=x.dtype, device=x.device))
+    return _Dropout.apply(x, p, key, offset)
+
+
+_zero_cells = {}
+ZERO_CELLS = 1024
+
+
+def _zeroed_cell(like: torch.Tensor) -> Optional[torch.Tensor]:
+    """An absmax cell that holds 0, for a kernel that takes its maximum with atomics in ONE launch: cells are dealt out of a pool
+    zeroed ZERO_CELLS at a time (per device and stream, as _workspace) and never reused, so no call pays a fill launch."""
+    if not FUSE_ABSMAX:
+        return None
+    key = (like.device.index, _stream())
+    pool = _zero_cells.get(key)
+    if pool is None or pool[1] >= ZERO_CELLS:
+        pool = _zero_cells[key] = [torch.zeros(ZERO_CELLS, dtype=torch.int32, device=like.device), 0]
+    cell = pool[0][pool[1]:pool[1] + 1]
+    pool[1] += 1
+    return cell
+
+
+class _DropPathAddRelu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, residual, scale, call):
+        lib = _lib.load()
+        b16 = z.dtype == torch.bfloat16
+        req = _req16 if b16 else _req
+        z, res = req(z, "drop_path branch"), req(residual, "drop_path residual")
+        y = torch.empty_like(z)
+        cell = None if b16 else _zeroed_cell(z)
+        n = z.numel()
+        check(lib.cstp_droppath_add_relu_forward(_stream(), z.data_ptr(), res.data_ptr(), scale.data_ptr(), y.data_ptr(), n,
+                                                 n // z.shape[0], 1 if b16 else 0, _ptr(cell)), "cstp_droppath_add_relu_forward")
+        call.cell = cell
+        ctx.save_for_backward(y, scale)
+        ctx.b16 = b16
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        y, scale = ctx.saved_tensors
+        need_z, need_r = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_z or need_r):
+            return None, None, None, None
+        dy = (_req16 if ctx.b16 else _req)(dy, "drop_path grad_output")
+        dz = torch.empty_like(y) if need_z else None
+        dres = torch.empty_like(y) if need_r else None
+        n = y.numel()
+        check(lib.cstp_droppath_add_relu_backward(_stream(), y.data_ptr(), dy.data_ptr(), scale.data_ptr(), _ptr(dz), _ptr(dres), n,
+                                                  n // y.shape[0], 1 if ctx.b16 else 0), "cstp_droppath_add_relu_backward")
+        return dz, dres, None, None
+
+
+def drop_path_add_relu(z, residual, scale):
+    """relu(scale[b] * z[b] + residual[b]): the end of a residual block under stochastic depth, one launch forward and one backward
+    (cstp_droppath_add_relu_*).  z / residual: [B, ...] of one shape, both fp32 or both bf16 (bf16 storage: fp32 arithmetic,
+    rounded to nearest even); scale: fp32 [B] on the device, 0 for a dropped sample and 1 / (1 - p) for a kept one.  The fp32
+    result carries its absmax for the consuming convolution."""
+    for name, t in (("branch", z), ("residual", residual), ("scale", scale)):
+        if not t.is_cuda:
+            raise _lib.CstpError("drop_path %s must be on a HIP device (cstp_amd has no CPU path)" % name)
+    if z.dim() < 2 or residual.shape != z.shape or residual.dtype != z.dtype:
+        raise _lib.CstpError("drop_path residual %s %s != branch %s %s" % (tuple(residual.shape), residual.dtype, tuple(z.shape), z.dtype))
+    if z.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.CstpError("drop_path activations must be float32 or bfloat16, got %s" % (z.dtype,))
+    if scale.dtype != torch.float32 or scale.shape != (z.shape[0],) or z.shape[0] == 0 or z.numel() == 0:
+        raise _lib.CstpError("drop_path scale must be float32 [%d] for a non-empty batch" % (z.shape[0],))
+    scale = scale.contiguous()
+    if not REG_FUSED:
+        s = scale.view((-1,) + (1,) * (z.dim() - 1))
+        if z.dtype == torch.bfloat16:
+            return torch.relu(s * z.float() + residual.float()).to(torch.bfloat16)
+        return torch.relu(s * z + residual)
+    call = _Call()
+    y = _DropPathAddRelu.apply(z, residual, scale, call)
+    _tag_absmax(y, call.cell)
+    return y
+
+
 class _NTXent(torch.autograd.Function):
     @staticmethod
     def forward(ctx, reps, temperature):

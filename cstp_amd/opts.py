@@ -21,6 +21,11 @@ Additions (all optional, defaults reproduce the reference):
   --mix_switch_prob  fine-tuning: probability of CutMix when both alphas are positive (default 0.5)
                      (cstp_amd/mix.py; validation keeps the plain cross-entropy; main_byol.py, test.py and retrieval.py
                      ignore all five)
+  --dropout          fine-tuning: dropout probability on the classifier's input in train mode, in [0, 1) (default 0 = off); every
+                     backbone, ft_fc and ft_all (i3d_byol: the probability of its own dropout module)
+  --drop_path        fine-tuning: stochastic depth on the residual blocks of r21d_byol / r3d_byol, in [0, 1) (default 0 = off):
+                     block l of L is dropped per sample with P * l / (L - 1); refused for s3d_byol, i3d_byol and --task ft_fc
+                     (cstp_amd/regularize.py; validation, main_byol.py, test.py, retrieval.py and knn.py never regularise)
   --knn_k           weighted k-NN classification (knn.py, the --knn_every monitor): neighbours per query, 1..64 (default 20)
   --knn_t           its temperature: neighbour j weighs exp((sim_j - sim_0) / T), must be > 0 (default 0.07)
   --knn_every       main_byol.py: after every E-th epoch and after the last, rank 0 classifies the labelled test videos by k-NN
@@ -119,6 +124,8 @@ _FLAGS = [
     ("cutmix_alpha", 0.0, float, "main_ft_mp.py: CutMix, lam ~ Beta(alpha, alpha) once per batch, one box through all frames (0 = off)"),
     ("mix_prob", 1.0, float, "main_ft_mp.py: probability that a batch is mixed (with --mixup_alpha / --cutmix_alpha)"),
     ("mix_switch_prob", 0.5, float, "main_ft_mp.py: probability of CutMix instead of mixup when both alphas are positive"),
+    ("dropout", 0.0, float, "main_ft_mp.py: dropout probability in front of the classifier, in [0, 1) (0 = off)"),
+    ("drop_path", 0.0, float, "main_ft_mp.py: stochastic depth on the residual blocks of r21d_byol / r3d_byol, linear rule, in [0, 1) (0 = off)"),
     ("knn_every", 0, int, "main_byol.py: k-NN top-1 of the online encoder after every E-th epoch and after the last (0 = off)"),
 ]
 RETRIEVAL_MAX_K = 64      # ops.SIM_TOPK_MAX_K: one lane per list slot

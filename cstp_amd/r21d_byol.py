@@ -265,7 +265,12 @@ class SpatioTemporalResBlock(nn.Module):
         self.bn2 = BatchNorm3d(out_channels)
         self.outrelu = ReLU()
 
+    _drop_scale = None      # stochastic depth: this block's per-sample branch scale for ONE training forward (ByolBase.regularized)
+
     def forward(self, x, groups=1):
+        scale = self._drop_scale if self.training else None
+        if scale is not None:
+            return self._forward_drop_path(x, groups, scale)
         # the block's input feeds two ops -- conv1 and the residual addition (or, in a downsample block, conv1 and the shortcut
         # convolution): their two gradients are summed inside the second op's kernel instead of by a separate add pass
         join = ops.GradJoin(2) if (self.training and torch.is_grad_enabled() and x.requires_grad
@@ -277,6 +282,17 @@ class SpatioTemporalResBlock(nn.Module):
             join = None
         # relu(x + bn2(res)) as one kernel (r21d_byol.py:143,148)
         return self.bn2(res, residual=x, relu=True, groups=groups, grad_join=join)
+
+    def _forward_drop_path(self, x, groups, scale):
+        """relu(x + scale[b] * bn2(res)): bn2 runs without residual and ReLU (its statistics may still come from the convolution's
+        epilogue) and ops.drop_path_add_relu joins the branch with x or the shortcut output.  The two gradients of the block's
+        input are summed by autograd here; a downsample block keeps the join of its two convolutions."""
+        join = ops.GradJoin(2) if (self.downsample and torch.is_grad_enabled() and x.requires_grad
+                                   and (x.dtype == torch.bfloat16 or not FUSE_BN_INTO_CONV)) else None
+        res = self.conv2(self.conv1(x, groups, grad_join=join, out_bn=self.bn1), groups, pre_bn=self.bn1, out_bn=self.bn2)
+        if self.downsample:
+            x = self.downsamplebn(self.downsampleconv(x, groups, grad_join=join, out_bn=self.downsamplebn), groups=groups)
+        return ops.drop_path_add_relu(self.bn2(res, groups=groups), x, scale)
 
 
 class SpatioTemporalResLayer(nn.Module):
@@ -365,6 +381,24 @@ class ByolBase(nn.Module):
     act_bf16 = False           # True: the clip pair is rounded to bf16 once (bf16 activation storage)
     ROT_HEAD = "rotate_cls"    # attribute name of the rotation head (the reference's wrappers spell it two ways)
     _grad_stage_cb = None      # set by the data-parallel training step: called with a stage index during backward
+    _dropout = None            # (p, key) of the classifier dropout for ONE training forward (regularized), else None
+
+    def residual_blocks(self):
+        """The online encoder's residual blocks in forward order across the stages: the blocks stochastic depth numbers
+        (registration order is forward order in both residual backbones; none for S3D-G and I3D)."""
+        return [m for m in self.online_net.modules() if hasattr(type(m), "_drop_scale")]
+
+    def regularized(self, dropout=None, drop_scales=None):
+        """Context manager: within it a TRAINING forward applies ``dropout`` = (p, key) to the classifier's input and
+        ``drop_scales`` = [fp32 [batch] device tensor, or None for a block that is never dropped] to residual_blocks().  Everything
+        is removed on exit, so eval forwards and later steps run the unregularised paths."""
+        return _Regularized(self, dropout, drop_scales)
+
+    def _head_dropout(self, feat):
+        """The classifier's input under --dropout: a no-op outside a regularized() training forward."""
+        if self.training and self._dropout is not None:
+            return ops.dropout(feat, self._dropout[0], self._dropout[1], 0)
+        return feat
 
     def grad_stage_slices(self):
         """[(offset, numel)] of the flat gradient arena per gradient stage, in the order the backward pass completes them
@@ -563,7 +597,7 @@ class ByolBase(nn.Module):
         built without ``norm`` or o_type is 'scratch'."""
         if norm and o_type != "scratch":
             feat = self.classify_bn(ops.l2_normalize(feat))
-        out = self.classify(feat)
+        out = self.classify(self._head_dropout(feat))
         if self.training and self._arenas is not None:
             self._arenas["nbt"]["all"] += 1
             if norm and o_type == "scratch":
@@ -657,6 +691,29 @@ class ByolBase(nn.Module):
         return loss.mean(), (pred_spa, pred_tem, pred_pb[:b], pred_pb[b:], pred_rot[:b], pred_rot[b:])
 
 
+class _Regularized:
+    """ByolBase.regularized: installs the step's dropout key and per-block drop-path scales, removes them on exit."""
+
+    def __init__(self, model, dropout, drop_scales):
+        self.model, self.dropout, self.drop_scales = model, dropout, drop_scales
+
+    def __enter__(self):
+        m = self.model
+        self.blocks = m.residual_blocks() if self.drop_scales is not None else []
+        if len(self.blocks) != (len(self.drop_scales) if self.drop_scales is not None else 0):
+            raise ValueError("%d drop-path scales for %d residual blocks" % (len(self.drop_scales), len(self.blocks)))
+        m._dropout = self.dropout
+        for blk, sc in zip(self.blocks, self.drop_scales or ()):
+            blk._drop_scale = sc
+        return m
+
+    def __exit__(self, *exc):
+        self.model._dropout = None
+        for blk in self.blocks:
+            blk._drop_scale = None
+        return False
+
+
 class R21DBYOL(ByolBase):
     """forward(x1, x2, o_type='loss_com') -> (loss_byol, (pred_spa, pred_tem, pred_pb_1, pred_pb_2,
     pred_rot_1, pred_rot_2)) exactly as r21d_byol.py:357-382."""
@@ -708,7 +765,7 @@ class R21DBYOL(ByolBase):
             if self.cls_bn is False or self.cls_bn is None:
                 raise TypeError("'bool' object is not callable")    # the reference calls self.cls_bn unconditionally (:397)
             online_feat = self.cls_bn(online_feat)                  # :397
-            out = self.classify(online_feat)                        # :398
+            out = self.classify(self._head_dropout(online_feat))    # :398 (--dropout: in front of the classifier)
             if self.training and self._arenas is not None:
                 self._arenas["nbt"]["all"] += 1
             return out

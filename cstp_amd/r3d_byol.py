@@ -84,7 +84,15 @@ class BasicBlock(nn.Module):
         self.downsample = downsample
         self.stride = stride
 
+    _drop_scale = None      # stochastic depth: this block's per-sample branch scale for ONE training forward (ByolBase.regularized)
+
     def forward(self, x, groups=1):
+        scale = self._drop_scale if self.training else None
+        if scale is not None:
+            # relu(residual + scale[b] * bn2(.)): bn2 alone, then the join kernel; autograd sums the input's two gradients
+            out = self.conv2(self.bn1(self.conv1(x), relu=True, groups=groups))
+            res = x if self.downsample is None else self.downsample(x, groups)
+            return ops.drop_path_add_relu(self.bn2(out, groups=groups), res, scale)
         join = _residual_join(self, x)
         out = self.bn1(self.conv1(x, grad_join=join), relu=True, groups=groups)            # relu(bn1(conv1 x))   :84-86
         out = self.conv2(out)
@@ -111,7 +119,15 @@ class Bottleneck(nn.Module):
         self.downsample = downsample
         self.stride = stride
 
+    _drop_scale = None      # stochastic depth: as BasicBlock
+
     def forward(self, x, groups=1):
+        scale = self._drop_scale if self.training else None
+        if scale is not None:
+            out = self.bn1(self.conv1(x), relu=True, groups=groups)
+            out = self.conv3(self.bn2(self.conv2(out), relu=True, groups=groups))
+            res = x if self.downsample is None else self.downsample(x, groups)
+            return ops.drop_path_add_relu(self.bn3(out, groups=groups), res, scale)
         join = _residual_join(self, x)
         out = self.bn1(self.conv1(x, grad_join=join), relu=True, groups=groups)
         out = self.bn2(self.conv2(out), relu=True, groups=groups)

@@ -312,9 +312,13 @@ class FineTuneStep:
     buffers are broadcast from rank 0 at the top of each step (see PretrainStep).
     ``mixer`` (cstp_amd.mix.Mixer; None = exactly the step above): per step one plan of (seed, epoch, step, rank) is drawn, the
     batch is blended in one launch (ops.clip_mix; skipped for an identity plan) and the loss is ops.soft_cross_entropy against the
-    sample's and its partner's labels with the mixer's label smoothing.  Ranks draw different plans; nothing is communicated."""
+    sample's and its partner's labels with the mixer's label smoothing.  Ranks draw different plans; nothing is communicated.
+    ``regularizer`` (cstp_amd.regularize.Regularizer; None = exactly the step above): per step one plan of the same (seed, epoch,
+    step, rank) gives the key of the dropout mask in front of the classifier and the per-sample, per-block drop-path scales; the
+    whole scale table travels in one pinned, asynchronous upload (no host read, no synchronise) and the model carries the plan for
+    that one forward only.  A model in eval mode, or a block whose drop probability is 0, runs the unregularised code."""
 
-    def __init__(self, model, optimizer, task, flat_allreduce=True, cross_entropy=None, mixer=None):
+    def __init__(self, model, optimizer, task, flat_allreduce=True, cross_entropy=None, mixer=None, regularizer=None):
         self._ce = cross_entropy if cross_entropy is not None else ops.cross_entropy
         if task not in ("ft_fc", "ft_all"):
             raise ValueError("o_type %r: the classifier forward serves 'ft_fc' / 'ft_all' (r21d_byol.py:394)" % (task,))
@@ -329,6 +333,17 @@ class FineTuneStep:
         self.mixer = mixer
         self._epoch, self._step = 0, 0
         self.last_plan = None
+        # dropout / stochastic depth (cstp_amd/regularize.py); None: the step above, untouched
+        self.regularizer = regularizer
+        self.last_reg_plan = None
+        self._inner = inner
+        if regularizer is not None:
+            self._n_blocks = len(inner.residual_blocks())
+            if regularizer.drop_path > 0.0:
+                if self._n_blocks == 0:
+                    raise ValueError("--drop_path: %s has no residual branch to drop" % type(inner).__name__)
+                if task == "ft_fc":
+                    raise ValueError("--drop_path with ft_fc: nothing inside a dropped branch is trained")
 
     def set_epoch(self, epoch):
         """Positions the mixer's plans: they are functions of (seed, epoch, step within the epoch, rank), so a resumed run that
@@ -348,7 +363,6 @@ class FineTuneStep:
         mixer = self.mixer
         rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
         plan = mixer.plan(inputs.shape[0], inputs.shape[-2], inputs.shape[-1], self._epoch, self._step, rank)
-        self._step += 1
         self.last_plan = plan
         if plan.identity:
             self._partner_targets = targets
@@ -360,15 +374,32 @@ class FineTuneStep:
         lam = torch.full((inputs.shape[0],), plan.lam, dtype=torch.float32, device=targets.device)
         return inputs, lambda out: ops.soft_cross_entropy(out, targets, tb, lam, mixer.label_smoothing)
 
+    def _regularized(self, inputs):
+        """-> the context under which the model runs this step's forward: its dropout key and drop-path scales installed."""
+        reg = self.regularizer
+        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        plan = self.last_reg_plan = reg.plan(inputs.shape[0], self._n_blocks, self._epoch, self._step, rank)
+        scales = None
+        if plan.scale is not None:
+            # the whole [blocks][batch] table in one pinned, asynchronous upload; a block that is never dropped gets no row
+            host = torch.from_numpy(plan.scale)
+            table = (host.pin_memory() if inputs.is_cuda else host).to(inputs.device, non_blocking=True)
+            scales = [table[l] if plan.p[l] > 0.0 else None for l in range(self._n_blocks)]
+        dropout = (reg.dropout, plan.key) if plan.key is not None else None
+        return self._inner.regularized(dropout, scales)
+
     def __call__(self, inputs, targets):
         if self._flat:
             sync_buffers(self.model)
         loss_fn = None
         if self.mixer is not None:
             inputs, loss_fn = self._mixed(inputs, targets)
+        reg_ctx = self._regularized(inputs) if self.regularizer is not None else contextlib.nullcontext()
+        self._step += 1                       # the mixer's and the regulariser's plans share (epoch, step)
         sync_ctx = self.model.no_sync() if self._flat else contextlib.nullcontext()
         with sync_ctx:
-            outputs = self.model(inputs, o_type=self.task)
+            with reg_ctx:                     # (the plan leaves the model when the forward is through, whether it raised or not)
+                outputs = self.model(inputs, o_type=self.task)
             loss = self._ce(outputs, targets) if loss_fn is None else loss_fn(outputs)
             self.optimizer.zero_grad()
             loss.backward()

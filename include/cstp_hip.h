@@ -667,6 +667,30 @@ int cstp_simtopk(void* stream, const float* q, const float* g, int32_t nq, int32
 int cstp_knn_vote(void* stream, const float* val, const int32_t* idx, const int32_t* g_labels, int32_t nq, int32_t ng,
                   int32_t k, float inv_t, int32_t n_top, int32_t* pred, float* score);
 
+/* ---- fine-tuning regularisers: dropout and the stochastic-depth residual join (csrc/reg.h) -----------
+ * Philox4x32-10 (Salmon et al., SC'11) on the host: out4 = Philox(ctr4, key2).  The function the dropout kernel evaluates,
+ * exported so that its known answers can be checked without a device. */
+int cstp_philox4x32_10(const uint32_t* ctr4, const uint32_t* key2, uint32_t* out4);
+/* Dropout with a counter-based mask, fp32, x [n] -> y [n] (y may alias x).  For element e:
+ *   ctr = (lo32(e >> 2), hi32(e >> 2), lo32(offset), hi32(offset)),  key = (lo32(seed), hi32(seed))
+ *   w   = Philox4x32-10(ctr, key)[e & 3],   u = (w >> 8) * 2^-24 (exact in fp32)
+ *   y   = u >= p ? x * (1.0f / (1.0f - p)) : 0
+ * No mask tensor exists: the backward pass is the same call on dy with the same (seed, offset).  offset numbers the call site
+ * (the classifier head uses 0).  One Philox evaluation serves four consecutive elements; 16-byte accesses where x and y are
+ * 16-byte aligned, element accesses for the tail and for unaligned views, with the same bits.  One launch, no atomics.
+ * Refused before any HIP call: null pointers, n <= 0, p outside [0, 1) (NaN included). */
+int cstp_dropout(void* stream, const float* x, float* y, int64_t n, float p, uint64_t seed, uint64_t offset);
+/* Stochastic depth at the end of a residual block: y[b][i] = relu(scale[b] * z[b][i] + res[b][i]), rows of row = C*D*H*W
+ * elements, n = samples * row.  z, res, y: all fp32 (bf16 == 0) or all bf16 (bf16 != 0: computed in fp32, rounded to nearest
+ * even).  scale [samples] fp32: 0 for a dropped sample, 1 / (1 - p) for a kept one.  The sample index is a grid dimension.
+ * y_absmax (optional, fp32 only): a cell that HOLDS 0 ON ENTRY and receives max |y| as an fp32 bit pattern, one atomicMax per
+ * block (the only atomic; a cell that held something larger keeps it: an over-estimate).  One launch. */
+int cstp_droppath_add_relu_forward(void* stream, const void* z, const void* res, const float* scale, void* y, int64_t n,
+                                   int64_t row, int32_t bf16, uint32_t* y_absmax);
+/* g = dy where y > 0, else 0;  dz = scale[b] * g;  dres = g.  One launch writes both; either output may be NULL (not both). */
+int cstp_droppath_add_relu_backward(void* stream, const void* y, const void* dy, const float* scale, void* dz, void* dres,
+                                    int64_t n, int64_t row, int32_t bf16);
+
 #ifdef __cplusplus
 }
 #endif

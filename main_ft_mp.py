@@ -25,7 +25,9 @@ What differs (each a fix of something that cannot work in the reference, none ch
     --n_workers JPEG decode threads; cstp_amd.frame_folder).
 What is added (off by default, then the step is the one above): --label_smoothing, --mixup_alpha, --cutmix_alpha, --mix_prob,
 --mix_switch_prob regularise TRAINING with smoothed / mixed targets and blended clips (cstp_amd.mix, cstp_clip_mix,
-cstp_soft_cross_entropy_*); training accuracy is then taken against the target that carried the larger weight.
+cstp_soft_cross_entropy_*); training accuracy is then taken against the target that carried the larger weight.  --dropout and
+--drop_path add dropout in front of the classifier and stochastic depth on the residual blocks (cstp_amd.regularize, cstp_dropout,
+cstp_droppath_add_relu_*), in training forwards only.
 """
 from __future__ import annotations
 
@@ -42,6 +44,7 @@ from cstp_amd import ops
 from cstp_amd.mix import build_mixer
 from cstp_amd.model import generate_model
 from cstp_amd.optim import build_optimizer
+from cstp_amd.regularize import build_regularizer
 from cstp_amd.opts import parse_opts
 from cstp_amd.device_batches import DeviceBatches
 from cstp_amd.scheduler import ReduceLROnPlateau
@@ -198,6 +201,7 @@ def main_worker(local_rank, opts):
     opts.arch = "{}-{}".format(opts.model_name, opts.model_depth)
     if opts.task not in TRAIN_TASKS:
         raise ValueError("main_ft_mp.py serves --task %s, got %r" % ("/".join(TRAIN_TASKS), opts.task))
+    regularizer = build_regularizer(opts)        # --dropout / --drop_path: refused here, before any data or model is built
 
     print("Preprocessing train data ...")
     train_data = build_dataset(opts, "train")
@@ -232,7 +236,8 @@ def main_worker(local_rank, opts):
     scheduler = ReduceLROnPlateau(optimizer, "min", patience=opts.lr_patience)
     # --label_smoothing / --mixup_alpha / --cutmix_alpha (all tasks served here); None at the defaults.  Training only:
     # validation below keeps the plain cross-entropy, so the plateau scheduler's metric stays comparable between runs
-    step_fn = FineTuneStep(model, optimizer, o_type_for(opts.task), mixer=build_mixer(opts))
+    # --dropout / --drop_path likewise: None at the defaults, training forwards only
+    step_fn = FineTuneStep(model, optimizer, o_type_for(opts.task), mixer=build_mixer(opts), regularizer=regularizer)
 
     for epoch in range(begin_epoch, opts.n_epochs + 1):
         print("Start to fine-tune")
