@@ -198,6 +198,11 @@ SIGNATURES = {
     "cstp_dropout": (c_int32, [_P, _P, _P, c_int64, c_float, c_uint64, c_uint64]),
     "cstp_droppath_add_relu_forward": (c_int32, [_P, _P, _P, _P, _P, c_int64, c_int64, c_int32, _P]),
     "cstp_droppath_add_relu_backward": (c_int32, [_P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int32]),
+    # linear probe on cached features: classifier step and ranking (csrc/probe.h)
+    "cstp_probe_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "cstp_probe_step": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P,
+                                  c_size_t]),
+    "cstp_probe_predict": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P]),
 }
 
 _lib = None

@@ -360,3 +360,5 @@ extern "C" int cstp_knn_vote(void* stream, const float* val, const int32_t* idx,
   CSTP_LAUNCH_CHECK();
   return 0;
 }
+
+#include "probe.h"  // the linear probe on cached features: cstp_probe_step, cstp_probe_predict

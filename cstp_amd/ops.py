@@ -2054,6 +2054,116 @@ def knn_vote(val, idx, g_labels, temperature, n_top=5):
     return pred, score
 
 
+PROBE_MAX_CLASSES = 1024
+PROBE_MAX_TOP = 8
+
+
+def _probe_operands(op, x, w, b, mean, inv_std):
+    """The shared checks of probe_step / probe_predict on (x [n, d], w [c, d], b [c], mean / inv_std [d] or None) -> (n, d, c)."""
+    if x.dim() != 2:
+        raise _lib.CstpError("%s: x must be [rows, features], got %s" % (op, tuple(x.shape)))
+    if w.dim() != 2 or w.shape[1] != x.shape[1]:
+        raise _lib.CstpError("%s: w must be [classes, %d], got %s" % (op, x.shape[1], tuple(w.shape)))
+    n, d = x.shape
+    c = w.shape[0]
+    if b.dim() != 1 or b.shape[0] != c:
+        raise _lib.CstpError("%s: b must be [%d], got %s" % (op, c, tuple(b.shape)))
+    for t, name in ((mean, "mean"), (inv_std, "inv_std")):
+        if t is not None and (t.dim() != 1 or t.shape[0] != d):
+            raise _lib.CstpError("%s: %s must be [%d], got %s" % (op, name, d, tuple(t.shape)))
+    for t, name in ((x, "x"), (w, "w"), (b, "b"), (mean, "mean"), (inv_std, "inv_std")):
+        if t is not None and t.dtype != torch.float32:
+            raise _lib.CstpError("%s: %s must be float32, got %s" % (op, name, t.dtype))
+    if not 2 <= c <= PROBE_MAX_CLASSES:
+        raise _lib.CstpError("%s: the number of classes c must be in 2..%d, got %d" % (op, PROBE_MAX_CLASSES, c))
+    if n < 1 or d < 1:
+        raise _lib.CstpError("%s: empty operand, x is %s" % (op, tuple(x.shape)))
+    return n, d, c
+
+
+def _probe_devices(op, named):
+    named = [(t, name) for t, name in named if t is not None]
+    for t, name in named:
+        if not t.is_cuda:
+            raise _lib.CstpError("%s: %s must be on a HIP device (cstp_amd has no CPU path)" % (op, name))
+    for t, name in named[1:]:
+        if t.device != named[0][0].device:
+            raise _lib.CstpError("%s: %s on %s, %s on %s" % (op, named[0][1], named[0][0].device, name, t.device))
+
+
+def _probe_c(op, t, name):
+    if not t.is_contiguous():
+        raise _lib.CstpError("%s: %s must be contiguous" % (op, name))
+    return t
+
+
+def probe_step(x, labels, w, b, rows=None, mean=None, inv_std=None, out=None):
+    """One step of a softmax classifier on rows gathered from the feature matrix x [n, d] fp32 (include/cstp_hip.h:
+    cstp_probe_step): labels [n] int64 indexed by the gathered row, rows [m] int32 or None (the whole matrix in order),
+    mean / inv_std [d] fp32 or None standardise on load, w [c, d], b [c] -> (loss [1] fp32, hits [1] int32, dw [c, d], db [c]):
+    the mean cross-entropy of the batch, the number of rows whose arg-max class is their label, and the gradients of the loss.
+    ``out`` = (loss, hits, dw, db) preallocated, contiguous and not aliasing w / b: then nothing is allocated.  Three launches,
+    no atomics, no host read, equal bits on equal inputs.  Not an autograd Function: the caller owns the update."""
+    op = "probe_step"
+    n, d, c = _probe_operands(op, x, w, b, mean, inv_std)
+    if labels.dim() != 1 or labels.shape[0] != n:
+        raise _lib.CstpError("%s: labels must be [%d], one per row of x, got %s" % (op, n, tuple(labels.shape)))
+    if labels.dtype != torch.int64:
+        raise _lib.CstpError("%s: labels must be int64, got %s" % (op, labels.dtype))
+    if rows is not None:
+        if rows.dim() != 1 or rows.shape[0] < 1:
+            raise _lib.CstpError("%s: rows must be a non-empty [m] vector, got %s" % (op, tuple(rows.shape)))
+        if rows.dtype != torch.int32:
+            raise _lib.CstpError("%s: rows must be int32, got %s" % (op, rows.dtype))
+    m = n if rows is None else rows.shape[0]
+    if out is not None:
+        if len(out) != 4:
+            raise _lib.CstpError("%s: out must be (loss, hits, dw, db)" % op)
+        for t, name, shape, dtype in ((out[0], "out loss", (1,), torch.float32), (out[1], "out hits", (1,), torch.int32),
+                                      (out[2], "out dw", (c, d), torch.float32), (out[3], "out db", (c,), torch.float32)):
+            if tuple(t.shape) != shape or t.dtype != dtype:
+                raise _lib.CstpError("%s: %s must be %s of shape %s, got %s %s" % (op, name, dtype, shape, t.dtype, tuple(t.shape)))
+    named = [(x, "x"), (labels, "labels"), (w, "w"), (b, "b"), (rows, "rows"), (mean, "mean"), (inv_std, "inv_std")]
+    if out is not None:
+        named += [(out[0], "out loss"), (out[1], "out hits"), (out[2], "out dw"), (out[3], "out db")]
+    _probe_devices(op, named)
+    for t, name in named:
+        if t is not None:
+            _probe_c(op, t, name)
+    lib = _lib.load()
+    if out is None:
+        out = (torch.empty(1, dtype=torch.float32, device=x.device), torch.empty(1, dtype=torch.int32, device=x.device),
+               torch.empty((c, d), dtype=torch.float32, device=x.device), torch.empty(c, dtype=torch.float32, device=x.device))
+    loss, hits, dw, db = out
+    ws = _workspace(x.device, lib.cstp_probe_workspace_bytes(m, d, c))
+    check(lib.cstp_probe_step(_stream(), x.data_ptr(), _ptr(rows), labels.data_ptr(), _ptr(mean), _ptr(inv_std), w.data_ptr(),
+                              b.data_ptr(), m, n, d, c, loss.data_ptr(), hits.data_ptr(), dw.data_ptr(), db.data_ptr(),
+                              ws.data_ptr(), ws.numel()), "cstp_probe_step")
+    return loss, hits, dw, db
+
+
+def probe_predict(x, w, b, mean=None, inv_std=None, n_top=5):
+    """The n_top best classes of every row of x [n, d] under the classifier (w [c, d], b [c]) on the features standardised on load
+    -> (pred [n, n_top] int32, score [n, n_top] fp32): classes by (logit descending, class id ascending) and their logits,
+    (-1, 0) where n_top > c -- the layout knn_vote writes, so knn.accuracy serves.  One launch, no logits table
+    (include/cstp_hip.h: cstp_probe_predict).  No autograd."""
+    op = "probe_predict"
+    n, d, c = _probe_operands(op, x, w, b, mean, inv_std)
+    if isinstance(n_top, bool) or not isinstance(n_top, int) or not 1 <= n_top <= PROBE_MAX_TOP:
+        raise _lib.CstpError("%s: n_top must be an int in 1..%d, got %r" % (op, PROBE_MAX_TOP, n_top))
+    named = [(x, "x"), (w, "w"), (b, "b"), (mean, "mean"), (inv_std, "inv_std")]
+    _probe_devices(op, named)
+    for t, name in named:
+        if t is not None:
+            _probe_c(op, t, name)
+    lib = _lib.load()
+    pred = torch.empty((n, n_top), dtype=torch.int32, device=x.device)
+    score = torch.empty((n, n_top), dtype=torch.float32, device=x.device)
+    check(lib.cstp_probe_predict(_stream(), x.data_ptr(), _ptr(mean), _ptr(inv_std), w.data_ptr(), b.data_ptr(), n, d, c, n_top,
+                                 pred.data_ptr(), score.data_ptr()), "cstp_probe_predict")
+    return pred, score
+
+
 # ----------------------------------------------------------------------------------------------
 # flat-arena utilities (no autograd)
 # ----------------------------------------------------------------------------------------------

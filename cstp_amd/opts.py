@@ -31,6 +31,12 @@ Additions (all optional, defaults reproduce the reference):
   --knn_every       main_byol.py: after every E-th epoch and after the last, rank 0 classifies the labelled test videos by k-NN
                     on the online encoder and logs top-1 in the ``acc`` column (default 0 = off); --dataset synthetic_video and
                     UcfRepreBYOLSpPre, --sample_size 112 | 224 (main_ft_mp.py, test.py and retrieval.py ignore all three)
+  --probe_epochs    linear probe on cached features (linear_probe.py): passes over the gallery features (default 100)
+  --probe_batch     its batch size in videos, 0 = one full batch per epoch (default 1024)
+  --probe_lr        its peak learning rate, a cosine to 0 over all steps, must be finite and > 0 (default 1e-3)
+  --probe_wd        its weight decay on the weight matrix, >= 0 (default 0; decoupled with adam, coupled with sgd)
+  --probe_optimizer adam | sgd (momentum 0.9) (default adam); the number of classes is --n_finetune_classes; the defaults are
+                    conventional choices, not tuned on real data (every other driver ignores all five)
 torchrun passes LOCAL_RANK through the environment instead of --local_rank; both are honoured.
 """
 from __future__ import annotations
@@ -152,6 +158,34 @@ def _knn_t(text):
     return t
 
 
+def _probe_epochs(text):
+    e = int(text)
+    if e < 1:
+        raise argparse.ArgumentTypeError("--probe_epochs must be >= 1, got %d" % e)
+    return e
+
+
+def _probe_batch(text):
+    b = int(text)
+    if b < 0:
+        raise argparse.ArgumentTypeError("--probe_batch must be >= 0 (0 = full batch), got %d" % b)
+    return b
+
+
+def _probe_lr(text):
+    v = float(text)
+    if not (v > 0.0 and v < float("inf")):
+        raise argparse.ArgumentTypeError("--probe_lr must be finite and > 0, got %r" % (text,))
+    return v
+
+
+def _probe_wd(text):
+    v = float(text)
+    if not (v >= 0.0 and v < float("inf")):
+        raise argparse.ArgumentTypeError("--probe_wd must be finite and >= 0, got %r" % (text,))
+    return v
+
+
 def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(description="CSTP pre-training on MI355X")
     for name, default, typ, text in _FLAGS:
@@ -168,6 +202,11 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--knn_k", default=20, type=_knn_k,
                         help="knn.py / --knn_every: neighbours per query, 1..%d" % RETRIEVAL_MAX_K)
     parser.add_argument("--knn_t", default=0.07, type=_knn_t, help="knn.py / --knn_every: temperature of the vote, > 0")
+    parser.add_argument("--probe_epochs", default=100, type=_probe_epochs, help="linear_probe.py: epochs over the gallery features")
+    parser.add_argument("--probe_batch", default=1024, type=_probe_batch, help="linear_probe.py: batch size, 0 = full batch")
+    parser.add_argument("--probe_lr", default=1e-3, type=_probe_lr, help="linear_probe.py: peak learning rate (cosine to 0), > 0")
+    parser.add_argument("--probe_wd", default=0.0, type=_probe_wd, help="linear_probe.py: weight decay on the weight matrix, >= 0")
+    parser.add_argument("--probe_optimizer", default="adam", choices=("adam", "sgd"), help="linear_probe.py: the update rule")
     return parser
 
 

@@ -667,6 +667,43 @@ int cstp_simtopk(void* stream, const float* q, const float* g, int32_t nq, int32
 int cstp_knn_vote(void* stream, const float* val, const int32_t* idx, const int32_t* g_labels, int32_t nq, int32_t ng,
                   int32_t k, float inv_t, int32_t n_top, int32_t* pred, float* score);
 
+/* ---- linear probe on cached features: a softmax classifier on frozen features (csrc/probe.h) --------------------------------
+ * x [n][d] fp32 is the feature matrix; d need not be a multiple of anything and the rows need not be 16-byte aligned.
+ * mean [d], inv_std [d] fp32 standardise on load, xs = (x - mean) * inv_std (either may be NULL: 0 and 1); no standardised copy
+ * is written.  w [c][d], b [c] fp32.  logit(r, k) = b[k] + sum_f xs[r][f] * w[k][f]: fp32 fmaf chain in feature order, bias last.
+ *
+ * cstp_probe_step: the batch is rows [m] int32 into x (NULL: rows 0..m-1, then m <= n); labels [n] int64 are indexed by the
+ * gathered row, y_r = labels[rows[r]].
+ *   loss[0] = mean_r -log_softmax(logit(r, .))[y_r]   soft-max about the row maximum, the mean over m accumulated in double
+ *   hits[0] = number of rows whose arg-max class is y_r (int32), ties going to the lowest class id
+ *   dw [c][d] = (1/m) sum_r (p_r - onehot(y_r)) xs_r^T,  db [c] = (1/m) sum_r (p_r - onehot(y_r))
+ * A label outside [0, c) follows the convention of cstp_soft_cross_entropy_* above: no one-hot mass, never used to form an
+ * address, and here the row contributes 0 to loss, gradients and hits; an index in rows outside [0, n) is treated the same way and
+ * is never dereferenced.  Such rows still count in m.
+ * Three launches whatever the sizes (logits + soft-max of 8-row slabs; dw over 64 x 64 tiles and S row slices; the fold of the
+ * slices, db, loss and hits), no atomics, no host read; every cross-row and cross-block sum has one fixed order, so equal inputs
+ * give equal bits.  Nothing is written outside loss, hits, dw, db and the first cstp_probe_workspace_bytes(m, d, c) bytes of ws:
+ *   cpad = 4 * ceil(c / 4);  S = max(1, min(32, ceil(m / 64), floor(512 / (ceil(d / 64) * ceil(c / 64)))))
+ *   bytes = 4 * m * cpad                     g = (p - onehot) / m, [m][cpad]
+ *         + round16(8 * m)                   row losses (fp32) and row hits (int32)
+ *         + round16(4 * S * c)               db per slice
+ *         + (S > 1 ? 4 * S * c * d : 0)      dw per slice
+ * (round16: up to a multiple of 16).  cstp_probe_workspace_bytes is a pure host function, non-decreasing in m, 0 on bad arguments.
+ *
+ * cstp_probe_predict: for every row 0..n-1 the n_top best classes by (logit descending, class id ascending) and their logits,
+ * pred / score [n][n_top] -- the layout cstp_knn_vote writes; (-1, 0.0f) where n_top > c.  One launch, no workspace, no logits
+ * table in memory, equal bits on equal inputs.
+ *
+ * Limits, refused with a message before any HIP call: m, n, d >= 1; 2 <= c <= 1024; c * d < 2^31; 1 <= n_top <= 8; no NULL
+ * among the required pointers (all but rows, mean, inv_std); dw / db overlapping w / b; ws not 16-byte aligned or smaller than
+ * cstp_probe_workspace_bytes(m, d, c). */
+size_t cstp_probe_workspace_bytes(int32_t m, int32_t d, int32_t c);
+int cstp_probe_step(void* stream, const float* x, const int32_t* rows, const int64_t* labels, const float* mean,
+                    const float* inv_std, const float* w, const float* b, int32_t m, int32_t n, int32_t d, int32_t c, float* loss,
+                    int32_t* hits, float* dw, float* db, void* ws, size_t ws_bytes);
+int cstp_probe_predict(void* stream, const float* x, const float* mean, const float* inv_std, const float* w, const float* b,
+                       int32_t n, int32_t d, int32_t c, int32_t n_top, int32_t* pred, float* score);
+
 /* ---- fine-tuning regularisers: dropout and the stochastic-depth residual join (csrc/reg.h) -----------
  * Philox4x32-10 (Salmon et al., SC'11) on the host: out4 = Philox(ctr4, key2).  The function the dropout kernel evaluates,
  * exported so that its known answers can be checked without a device. */
