@@ -28,6 +28,10 @@ __device__ __forceinline__ float4 ld4_last(const float* p) {
 }
 
 
+// the float4 / non-temporal-vector kernels take 16-byte accesses at base + row * s: every row must be a multiple of 4 floats AND
+// every tensor of the call 16-byte aligned (a contiguous view at a 4-byte storage offset is not); a null pointer is not accessed
+static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
 static inline int bn_nsplit(int n, int c) {
   int ns = cdiv(2048, c);
   if (ns > n) ns = n;
@@ -694,6 +698,46 @@ __global__ void bn1d_bwd_kernel(const float* __restrict__ x, const float* __rest
   dgamma[ch] = (accumulate ? dgamma[ch] : 0.f) + (float)t1;
 }
 
+// ... with the statistics REBUILT in fp64 from x and eps (cstp_bn1d_backward), and dx formed in fp64.  dx is the difference
+// g - mean(g) - xhat * mean(g xhat); with few rows per group it is eps / (var + eps) of the size of its terms (two rows:
+// exactly so, in every feature), which neither fp32 arithmetic nor an invstd rounded to fp32 can hold.  [B][F] tensors are the
+// heads' (a few thousand features, tens of rows): the extra pass over a column the thread has in cache costs nothing measurable.
+__global__ void bn1d_bwd_exact_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ dy,
+                                      const float* __restrict__ gamma, float* __restrict__ dx, float* __restrict__ dres,
+                                      float* __restrict__ dgamma, float* __restrict__ dbeta, int npg, int groups, int c,
+                                      float eps, int relu, int accumulate) {
+  const int ch = blockIdx.x * blockDim.x + threadIdx.x;
+  if (ch >= c) return;
+  double t0 = 0.0, t1 = 0.0;
+  const double ga = (double)gamma[ch];
+  for (int g = 0; g < groups; ++g) {
+    const size_t r0 = (size_t)g * npg;
+    double m0 = 0.0;
+    for (int r = 0; r < npg; ++r) m0 += (double)x[(r0 + r) * c + ch];
+    const double mu = m0 / npg;
+    double m1 = 0.0;
+    for (int r = 0; r < npg; ++r) { const double d = (double)x[(r0 + r) * c + ch] - mu; m1 += d * d; }
+    const double is = 1.0 / sqrt(m1 / npg + (double)eps);
+    double s0 = 0.0, s1 = 0.0;
+    for (int r = 0; r < npg; ++r) {
+      float gr = dy[(r0 + r) * c + ch];
+      if (relu && !(y[(r0 + r) * c + ch] > 0.f)) gr = 0.f;
+      s0 += (double)gr;
+      s1 += (double)gr * (((double)x[(r0 + r) * c + ch] - mu) * is);
+    }
+    t0 += s0; t1 += s1;
+    const double k = ga * is, mb = s0 / npg, mg = s1 / npg;
+    for (int r = 0; r < npg; ++r) {
+      float gr = dy[(r0 + r) * c + ch];
+      if (relu && !(y[(r0 + r) * c + ch] > 0.f)) gr = 0.f;
+      if (dres != nullptr) dres[(r0 + r) * c + ch] = gr;
+      dx[(r0 + r) * c + ch] = (float)(k * (((double)gr - mb) - ((double)x[(r0 + r) * c + ch] - mu) * is * mg));
+    }
+  }
+  dbeta[ch] = (accumulate ? dbeta[ch] : 0.f) + (float)t0;
+  dgamma[ch] = (accumulate ? dgamma[ch] : 0.f) + (float)t1;
+}
+
 
 // ---- eval mode: the running statistics are the statistics (r21d_byol.py cls/val/test under model.eval()) ----
 __global__ void bn_eval_prepare_kernel(const float* __restrict__ running_var, float* __restrict__ invstd, int c, float eps,
@@ -825,7 +869,7 @@ static int bn_forward_train_impl(void* stream, const float* x, const float* resi
   }
   double* part = reinterpret_cast<double*>(ws);
   const int ns = bn_nsplit(npg, c);
-  const bool v4 = (s % 4) == 0;
+  const bool v4 = (s % 4) == 0 && al16(x) && al16(residual) && al16(y);
   const dim3 rgrid(c, groups * ns);
   BnFin fin;
   memset(&fin, 0, sizeof(fin));
@@ -901,7 +945,7 @@ extern "C" int cstp_bn_forward_eval_am(void* stream, const float* x, const float
   unsigned* slots = y_absmax != nullptr ? reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + cstp_bn_eval_workspace_bytes(c)) : nullptr;
   hipLaunchKernelGGL(bn_eval_prepare_kernel, dim3(cdiv(c, 64)), dim3(64), 0, st, running_var, invstd, c, eps, y_absmax);
   CSTP_LAUNCH_CHECK();
-  const bool v4 = (s % 4) == 0;
+  const bool v4 = (s % 4) == 0 && al16(x) && al16(residual) && al16(y);
   const int chunks = cdiv(s, BN_UNROLL * 256 * (v4 ? 4 : 1));
   const dim3 agrid((unsigned)((size_t)n * c * chunks));
   // one "group" spanning the whole batch: the apply kernel reads mean/invstd at [channel]
@@ -930,7 +974,7 @@ extern "C" int cstp_bn_stats_train(void* stream, const float* x, const float* ga
   double* part = reinterpret_cast<double*>(ws);
   const int ns = bn_nsplit(npg, c);
   const dim3 rgrid(c, groups * ns);
-  if ((s % 4) == 0) hipLaunchKernelGGL((bn_reduce_kernel<0, true>), rgrid, dim3(256), 0, st, x, x, x, nullptr, nullptr, part, npg, c, s, ns, 0, nullptr);
+  if ((s % 4) == 0 && al16(x)) hipLaunchKernelGGL((bn_reduce_kernel<0, true>), rgrid, dim3(256), 0, st, x, x, x, nullptr, nullptr, part, npg, c, s, ns, 0, nullptr);
   else hipLaunchKernelGGL((bn_reduce_kernel<0, false>), rgrid, dim3(256), 0, st, x, x, x, nullptr, nullptr, part, npg, c, s, ns, 0, nullptr);
   CSTP_LAUNCH_CHECK();
   hipLaunchKernelGGL(bn_finalize_fwd_kernel, dim3(cdiv(c, 64)), dim3(64), 0, st, part, save_mean, save_invstd, running_mean,
@@ -985,7 +1029,7 @@ extern "C" int cstp_bn_backward_am(void* stream, const float* x, const float* y,
   const int ns = bn_nsplit(npg, c);
   float* gsum = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) +
                                          align_up((size_t)c * groups * ns * 2 * sizeof(double), 256));
-  const bool v4 = (s % 4) == 0;
+  const bool v4 = (s % 4) == 0 && al16(x) && al16(y) && al16(dy) && al16(dx) && al16(dresidual);   // (gout is dresidual)
   const dim3 rgrid(c, groups * ns);
   // residual + ReLU (a block's last BatchNorm): the reduction pass leaves the masked gradient in dresidual, the apply pass reads it
   const bool g_first = relu && y != nullptr && dresidual != nullptr && dresidual != dy;
@@ -1009,5 +1053,17 @@ extern "C" int cstp_bn_backward_am(void* stream, const float* x, const float* y,
     hipLaunchKernelGGL(absmax_fold_kernel, dim3(FOLD_BLOCKS), dim3(256), 0, st, slots, (int)agrid.x * 4, dx_absmax);
     CSTP_LAUNCH_CHECK();
   }
+  return 0;
+}
+
+extern "C" int cstp_bn1d_backward(void* stream, const float* x, const float* y, const float* dy, const float* gamma, float* dx,
+                                  float* dresidual, float* dgamma, float* dbeta, int32_t n, int32_t c, int32_t groups, float eps,
+                                  int32_t relu, int32_t accumulate) {
+  CSTP_REQUIRE(x && dy && gamma && dx && dgamma && dbeta, "null argument");
+  CSTP_REQUIRE(y != nullptr || !relu, "ReLU mask needs y");
+  CSTP_REQUIRE(n > 0 && c > 0 && groups > 0 && (n % groups) == 0 && eps >= 0.f, "bad shape");
+  hipLaunchKernelGGL(bn1d_bwd_exact_kernel, dim3(cdiv(c, 64)), dim3(64), 0, as_stream(stream), x, y, dy, gamma, dx, dresidual,
+                     dgamma, dbeta, n / groups, groups, c, eps, relu, accumulate ? 1 : 0);
+  CSTP_LAUNCH_CHECK();
   return 0;
 }

@@ -175,7 +175,7 @@ __global__ void ce_fwd_kernel(const float* __restrict__ logits, const int64_t* _
     for (int j = 1; j < k; ++j) mx = fmaxf(mx, p[j]);
     float se = 0.f;
     for (int j = 0; j < k; ++j) se += expf(p[j] - mx);
-    a += (double)(logf(se) + mx - p[labels[r]]);
+    a += (double)(logf(se) + (mx - p[labels[r]]));      // (mx - p first: a large common offset of the logits costs no digits)
   }
   a = block_sum(a, sm);
   if (threadIdx.x == 0) loss[0] = (float)(a / b);
@@ -200,13 +200,15 @@ __global__ void ce_bwd_kernel(const float* __restrict__ logits, const int64_t* _
 // One wave per row with the 64 lanes along k (k is 51 / 101 / 400 here); the row statistics come out of xor-shuffles, whose
 // order is fixed, so equal inputs give equal bits.  A target outside [0, k) carries no one-hot mass and is never an index.
 // tb == NULL: tb = ta;  lam == NULL: lam = 1.
+// Row statistics: mx = max_c p, se = sum_c exp(p - mx), sp = sum_c (p - mx).  Everything the loss adds is taken relative to mx,
+// so a common offset of the row's logits, however large, costs none of the loss's digits.
 __device__ __forceinline__ void soft_ce_row_stats(const float* __restrict__ p, int k, int lane, float& mx, float& se, float& sp) {
   float m = -INFINITY;
   for (int j = lane; j < k; j += 64) m = fmaxf(m, p[j]);
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
   float e = 0.f, s = 0.f;
-  for (int j = lane; j < k; j += 64) { const float v = p[j]; e += expf(v - m); s += v; }
+  for (int j = lane; j < k; j += 64) { const float v = p[j] - m; e += expf(v); s += v; }
   mx = m;
   se = wave_sum_all(e);
   sp = wave_sum_all(s);
@@ -224,12 +226,12 @@ __global__ void __launch_bounds__(1024) soft_ce_fwd_kernel(const float* __restri
     float mx, se, sp;
     soft_ce_row_stats(p, k, lane, mx, se, sp);
     if (lane == 0) {
-      const float lse = logf(se) + mx;
+      const float lg = logf(se);                       // the log-sum-exp relative to mx
       const int64_t a_ = ta[r], b_ = tb ? tb[r] : a_;
       const float l = lam ? lam[r] : 1.f;
-      const float na = (a_ >= 0 && a_ < k) ? lse - p[a_] : 0.f;
-      const float nb = (b_ >= 0 && b_ < k) ? lse - p[b_] : 0.f;
-      a += (double)((1.f - eps) * (l * na + (1.f - l) * nb) + eps * (lse - sp / (float)k));
+      const float na = (a_ >= 0 && a_ < k) ? lg + (mx - p[a_]) : 0.f;
+      const float nb = (b_ >= 0 && b_ < k) ? lg + (mx - p[b_]) : 0.f;
+      a += (double)((1.f - eps) * (l * na + (1.f - l) * nb) + eps * (lg - sp / (float)k));
     }
   }
   a = block_sum(a, sm);

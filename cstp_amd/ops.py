@@ -830,6 +830,7 @@ class _BNAct(torch.autograd.Function):
         ctx.remask = remask
         ctx.relu = relu
         ctx.groups = groups
+        ctx.eps = eps
         ctx.has_res = res is not None
         ctx.params = (gamma, beta)     # the parameter objects themselves (their .grad may be an arena slice, see backward)
         ctx.grad_join = grad_join
@@ -850,10 +851,15 @@ class _BNAct(torch.autograd.Function):
         ws = _workspace(x.device, nbytes)
         cell = _new_cell(x) if s > 1 else None
         with _span("bn_backward", (n, c, s, ctx.groups, ctx.has_res, bool(ctx.relu))):
-            check(lib.cstp_bn_backward_am(_stream(), x.data_ptr(), _ptr(y), dy.data_ptr(), gamma.data_ptr(), mean.data_ptr(),
-                                          invstd.data_ptr(), _ptr(ss), dx.data_ptr(), _ptr(dres), dgamma.data_ptr(),
-                                          dbeta.data_ptr(), n, c, s, ctx.groups, 1 if ctx.relu else 0, ws.data_ptr(), ws.numel(),
-                                          _ptr(cell), 1 if direct else 0), "cstp_bn_backward")
+            if s == 1:       # BatchNorm1d: the statistics rebuilt from x in fp64 (few rows per group: dx is a small difference)
+                check(lib.cstp_bn1d_backward(_stream(), x.data_ptr(), _ptr(y), dy.data_ptr(), gamma.data_ptr(), dx.data_ptr(),
+                                             _ptr(dres), dgamma.data_ptr(), dbeta.data_ptr(), n, c, ctx.groups, ctx.eps,
+                                             1 if ctx.relu else 0, 1 if direct else 0), "cstp_bn1d_backward")
+            else:
+                check(lib.cstp_bn_backward_am(_stream(), x.data_ptr(), _ptr(y), dy.data_ptr(), gamma.data_ptr(), mean.data_ptr(),
+                                              invstd.data_ptr(), _ptr(ss), dx.data_ptr(), _ptr(dres), dgamma.data_ptr(),
+                                              dbeta.data_ptr(), n, c, s, ctx.groups, 1 if ctx.relu else 0, ws.data_ptr(),
+                                              ws.numel(), _ptr(cell), 1 if direct else 0), "cstp_bn_backward")
         _tag_absmax(dx, cell)
         if dres is not None and ctx.grad_join is not None:       # the residual tensor's other consumer adds its gradient to this
             dres = ctx.grad_join.contribute(lambda: dres, lambda buf: buf.add_(dres))

@@ -283,6 +283,14 @@ int cstp_bn_backward_am(void* stream, const float* x, const float* y, const floa
                         float* dresidual, float* dgamma, float* dbeta, int32_t n, int32_t c, int32_t s, int32_t groups,
                         int32_t relu, void* ws, size_t ws_bytes, uint32_t* dx_absmax, int32_t accumulate);
 
+/* BatchNorm1d (x [n][c], s = 1) backward with the batch statistics REBUILT from x and eps in fp64 and dx formed in fp64: with
+ * few rows per group dx is eps / (var + eps) of the size of the terms it is the difference of (two rows: exactly that, in
+ * every feature), which an fp32 invstd cannot carry.  No saved statistics, no workspace; y (the forward output) is needed only
+ * with relu; dresidual may be NULL; accumulate as in cstp_bn_backward_am.  cstp_bn_backward with s = 1 remains (fp32 forms). */
+int cstp_bn1d_backward(void* stream, const float* x, const float* y, const float* dy, const float* gamma, float* dx,
+                       float* dresidual, float* dgamma, float* dbeta, int32_t n, int32_t c, int32_t groups, float eps,
+                       int32_t relu, int32_t accumulate);
+
 /* EVAL mode (model.eval(): main_ft_mp.py:254-262 validation, test.py:74-76): the running statistics are the
  * statistics -- y = act((x - running_mean) / sqrt(running_var + eps) * gamma + beta + residual); nothing is updated.
  * Forward only (the reference evaluates under torch.no_grad()).  ws: cstp_bn_eval_workspace_bytes(c) when s > 1. */
