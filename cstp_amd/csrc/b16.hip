@@ -1213,12 +1213,6 @@ __global__ void b16_avgpool_bwd_kernel(const float* __restrict__ dy, u16* __rest
 
 using namespace cstp;
 
-// CSTP_BN_SMALL=0: every BatchNorm through the two-launch sequence (A/B switch shared with bn.hip; read once)
-static bool b16_bn_small_on() {
-  static const bool on = [] { const char* e = getenv("CSTP_BN_SMALL"); return !(e && e[0] == '0'); }();
-  return on;
-}
-
 static inline unsigned b16_grid(size_t n, int per_block) {
   size_t b = (n + per_block - 1) / per_block;
   if (b > 65536) b = 65536;
@@ -1563,7 +1557,7 @@ extern "C" int cstp_b16_bn_forward_train(void* stream, const uint16_t* x, const 
   CSTP_REQUIRE(ws && ws_bytes >= cstp_b16_bn_workspace_bytes(n, c, s, groups), "workspace too small");
   hipStream_t st = as_stream(stream);
   const int npg = n / groups, ns = b16_bn_nsplit(npg, c);
-  if (b16_bn_small_on() && (size_t)npg * s <= (size_t)B16_SMALL_PT * 1024 && (size_t)n * c * s < (1ull << 31)) {
+  if ((size_t)npg * s <= (size_t)B16_SMALL_PT * 1024 && (size_t)n * c * s < (1ull << 31)) {
     float2* ss2 = reinterpret_cast<float2*>(scale_shift);
     if ((size_t)npg * s <= (size_t)B16_SMALL_PT * 256)
       hipLaunchKernelGGL(b16_bn_small_fwd_kernel<256>, dim3(c), dim3(256), 0, st, x, residual, y, gamma, beta, running_mean, running_var,
@@ -1599,7 +1593,7 @@ extern "C" int cstp_b16_bn_backward(void* stream, const uint16_t* x, const uint1
   CSTP_REQUIRE(ws && ws_bytes >= cstp_b16_bn_workspace_bytes(n, c, s, groups), "workspace too small");
   hipStream_t st = as_stream(stream);
   const int npg = n / groups, ns = b16_bn_nsplit(npg, c);
-  if (b16_bn_small_on() && (size_t)npg * s <= (size_t)B16_SMALL_PT * 256 && (size_t)n * c * s < (1ull << 31)) {
+  if ((size_t)npg * s <= (size_t)B16_SMALL_PT * 256 && (size_t)n * c * s < (1ull << 31)) {
     hipLaunchKernelGGL(b16_bn_small_bwd_kernel, dim3(c), dim3(256), 0, st, x, y, dy, gamma, save_mean, save_invstd,
                        reinterpret_cast<const float2*>(scale_shift), dx, dresidual, dgamma, dbeta, c, s, npg, groups, relu, accumulate ? 1 : 0);
     CSTP_LAUNCH_CHECK();

@@ -666,39 +666,7 @@ __global__ void bn1d_fwd_kernel(const float* __restrict__ x, const float* __rest
   if (running_mean != nullptr) { running_mean[ch] = rm; running_var[ch] = rv; }
 }
 
-__global__ void bn1d_bwd_kernel(const float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ dy,
-                                const float* __restrict__ gamma, const float* __restrict__ mean,
-                                const float* __restrict__ invstd, float* __restrict__ dx, float* __restrict__ dres,
-                                float* __restrict__ dgamma, float* __restrict__ dbeta, int npg, int groups, int c, int relu,
-                                int accumulate) {
-  const int ch = blockIdx.x * blockDim.x + threadIdx.x;
-  if (ch >= c) return;
-  double t0 = 0.0, t1 = 0.0;
-  const float ga = gamma[ch];
-  for (int g = 0; g < groups; ++g) {
-    const size_t r0 = (size_t)g * npg;
-    const float mu = mean[g * c + ch], is = invstd[g * c + ch];
-    double s0 = 0.0, s1 = 0.0;
-    for (int r = 0; r < npg; ++r) {
-      float gr = dy[(r0 + r) * c + ch];
-      if (relu && !(y[(r0 + r) * c + ch] > 0.f)) gr = 0.f;
-      s0 += (double)gr;
-      s1 += (double)(gr * ((x[(r0 + r) * c + ch] - mu) * is));
-    }
-    t0 += s0; t1 += s1;
-    const float k = ga * is, mb = (float)s0 / npg, mg = (float)s1 / npg;
-    for (int r = 0; r < npg; ++r) {
-      float gr = dy[(r0 + r) * c + ch];
-      if (relu && !(y[(r0 + r) * c + ch] > 0.f)) gr = 0.f;
-      if (dres != nullptr) dres[(r0 + r) * c + ch] = gr;
-      dx[(r0 + r) * c + ch] = k * (gr - mb - (x[(r0 + r) * c + ch] - mu) * is * mg);
-    }
-  }
-  dbeta[ch] = (accumulate ? dbeta[ch] : 0.f) + (float)t0;
-  dgamma[ch] = (accumulate ? dgamma[ch] : 0.f) + (float)t1;
-}
-
-// ... with the statistics REBUILT in fp64 from x and eps (cstp_bn1d_backward), and dx formed in fp64.  dx is the difference
+// The backward: statistics REBUILT in fp64 from x and eps (cstp_bn1d_backward), and dx formed in fp64.  dx is the difference
 // g - mean(g) - xhat * mean(g xhat); with few rows per group it is eps / (var + eps) of the size of its terms (two rows:
 // exactly so, in every feature), which neither fp32 arithmetic nor an invstd rounded to fp32 can hold.  [B][F] tensors are the
 // heads' (a few thousand features, tens of rows): the extra pass over a column the thread has in cache costs nothing measurable.
@@ -779,15 +747,10 @@ static unsigned* bn_slots(void* ws, int n, int c, int groups) {
                                      align_up((size_t)groups * c * 2 * sizeof(float), 256));
 }
 
-// CSTP_BN_SMALL=0: every BatchNorm3d through the three-launch sequence (A/B switch; read once)
-static bool bn_small_enabled() {
-  static const bool on = [] { const char* e = getenv("CSTP_BN_SMALL"); return !(e && e[0] == '0'); }();
-  return on;
-}
 // the single-launch kernels: <= 16 384 values per (channel, group), 32-bit element offsets, 16 slots per channel in the workspace
 static bool bn_small_ok(int n, int c, int s, int groups) {
   const size_t e = (size_t)(n / groups) * s;
-  return bn_small_enabled() && e <= (size_t)BN_SMALL_E && (size_t)n * c * s < (1ull << 31);
+  return e <= (size_t)BN_SMALL_E && (size_t)n * c * s < (1ull << 31);
 }
 
 extern "C" size_t cstp_bn_workspace_bytes(int32_t n, int32_t c, int32_t s, int32_t groups) {
@@ -999,18 +962,12 @@ extern "C" int cstp_bn_backward_am(void* stream, const float* x, const float* y,
                                    int32_t accumulate) {
   CSTP_REQUIRE(x && dy && gamma && save_mean && save_invstd && dx && dgamma && dbeta, "null argument");
   CSTP_REQUIRE(y != nullptr || !relu || scale_shift != nullptr, "ReLU mask needs y or scale_shift");
-  CSTP_REQUIRE(y != nullptr || s > 1, "BatchNorm1d backward needs y");
   const float2* ss2 = reinterpret_cast<const float2*>(scale_shift);
   CSTP_REQUIRE(n > 0 && c > 0 && s > 0 && groups > 0 && (n % groups) == 0, "bad shape");
+  // fp32 arithmetic on saved fp32 statistics cannot hold the backward of a [B][F] tensor (see bn1d_bwd_exact_kernel)
+  CSTP_REQUIRE(s > 1, "BatchNorm1d backward (s = 1): call cstp_bn1d_backward");
   const int npg = n / groups;
   hipStream_t st = as_stream(stream);
-  if (s == 1) {
-    CSTP_REQUIRE(dx_absmax == nullptr, "absmax by-product: BatchNorm3d (s > 1) only");
-    hipLaunchKernelGGL(bn1d_bwd_kernel, dim3(cdiv(c, 64)), dim3(64), 0, st, x, y, dy, gamma, save_mean, save_invstd, dx,
-                       dresidual, dgamma, dbeta, npg, groups, c, relu, accumulate ? 1 : 0);
-    CSTP_LAUNCH_CHECK();
-    return 0;
-  }
   CSTP_REQUIRE(ws && ws_bytes >= cstp_bn_workspace_bytes(n, c, s, groups), "workspace too small");
   // (the backward pass on 1024-thread blocks measured SLOWER than the three-launch sequence on the 14 x 14 stage -- 77 vs 56 us at
   //  576 channels: two tensors in registers per thread -- so only the 256-thread form is used here)

@@ -922,10 +922,9 @@ static bool stem_fits(const cstp_conv_desc& d, const ConvPlan& p) {
 // and no bias.  The tuner times plain forwards, where the gather kernel igemm_k1s wins the 64-row temporal layers of the
 // first stage (0.40 ms against 0.48 for igemm_k1w); WITH the transform the gather kernel pays it once per filter tap and cannot
 // leave the next BatchNorm's sums (0.524 ms + 0.075 ms of bn_reduce against 0.523 ms, sums included; same-box step A/B 56.57 ->
-// 55.97 ms, profiles/r04).  So such a call runs the weight-resident kernel wherever it applies (CSTP_K1W=0: the tuner's tile).
+// 55.97 ms, profiles/r04).  So such a call runs the weight-resident kernel wherever it applies.
 static bool k1w_preferred(const cstp_conv_desc& d, const Tile& t) {
-  static const bool on = [] { const char* e = getenv("CSTP_K1W"); return e == nullptr || atoi(e) != 0; }();
-  if (!on || g_force_tile != nullptr) return false;                 // (a pinned / timed tile is run as given)
+  if (g_force_tile != nullptr) return false;                // (a pinned / timed tile is run as given)
   if (!((t.sp == 1 || t.sp == 2) && t.mt == 4)) return false;      // the 64-row tiles of the gather / ring kernels
   return tpatch_geom_ok(d) && k1w_fits(d.k, d.c) && d.c <= KW_AFFC;
 }
@@ -949,11 +948,9 @@ static bool native_only() {
   return env_f32 || g_split_terms.load(std::memory_order_relaxed) == 1;
 }
 // Fully connected layers on <= 32 rows (linear.h): exact fp32 FMAs on weight-streaming kernels instead of a one-tile GEMM.
-// CSTP_LINEAR=0 keeps them on the convolution kernels; so do the native-f32 mode (every GEMM on v_mfma_f32 there) and a pinned /
-// timed tile.
+// The native-f32 mode (every GEMM on v_mfma_f32 there) and a pinned / timed tile keep them on the convolution kernels.
 static bool linear_shape(const cstp_conv_desc& d) {
-  static const bool on = [] { const char* e = getenv("CSTP_LINEAR"); return e == nullptr || atoi(e) != 0; }();
-  if (!on || g_force_tile != nullptr || native_only()) return false;
+  if (g_force_tile != nullptr || native_only()) return false;
   return d.d == 1 && d.h == 1 && d.w == 1 && d.kt == 1 && d.kh == 1 && d.kw == 1 && d.st == 1 && d.sh == 1 && d.sw == 1 &&
          d.pt == 0 && d.ph == 0 && d.pw == 0 && d.n <= LIN_NMAX;
 }
@@ -1402,13 +1399,13 @@ static void run_k1t(const Tile& tl, bool wres, hipStream_t s, const cstp_conv_de
   const int ntiles = d.n * g.ndt * g.nwt;
   const float2* ss = ia ? ia->ss : nullptr;
   if (wres) {
-#define CSTP_K1W_(ST_, AF_) \
+#define CSTP_KW_(ST_, AF_) \
   hipLaunchKernelGGL((igemm_k1w<ST_, AF_>), L.grid, dim3(512), 0, s, g, reinterpret_cast<const uint4*>(ws), src, out, L.t.inv_a, L.bcell, ntiles, L.part, L.pivot, L.zcell, ss)
-    if (L.part != nullptr && ss != nullptr) CSTP_K1W_(true, true);
-    else if (L.part != nullptr) CSTP_K1W_(true, false);
-    else if (ss != nullptr) CSTP_K1W_(false, true);
-    else CSTP_K1W_(false, false);
-#undef CSTP_K1W_
+    if (L.part != nullptr && ss != nullptr) CSTP_KW_(true, true);
+    else if (L.part != nullptr) CSTP_KW_(true, false);
+    else if (ss != nullptr) CSTP_KW_(false, true);
+    else CSTP_KW_(false, false);
+#undef CSTP_KW_
     return;
   }
 #define CSTP_K1T_(MT_, ST_, AF_) \
@@ -1440,9 +1437,8 @@ static void run_k1p(const Tile& tl, hipStream_t s, const cstp_conv_desc& d, bool
   g.rows_lds = patch_rows_needed(g.NF, g.H, g.W);
   {
     // staging by 16-byte loads (igemm_patch.h, QUAD): whole column quads, whole 8-channel groups, aligned lines, three rounds
-    static const bool quad_on = [] { const char* e = getenv("CSTP_K1P_QUAD"); return e == nullptr || atoi(e) != 0; }();
     const int lines = g.rows_lds / (g.W + 2);
-    g.quad = quad_on && (g.W & 3) == 0 && (g.Cs & 7) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 &&
+    g.quad = (g.W & 3) == 0 && (g.Cs & 7) == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0 &&
              lines * (g.W / 4) * 2 <= 192 && g.rows_lds + 32 <= KP_ROWS ? 1 : 0;
   }
   const K1pLaunch L = k1p_prepare(tl, s, d, dgrad, 9, w, src, ws, main_bytes, src_absmax, st);

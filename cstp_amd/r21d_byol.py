@@ -11,8 +11,8 @@ runs in the HIP kernels of libcstp_hip.so (cstp_amd.ops).  Differences from the 
 all additive:
   * ``layer_sizes`` is a constructor argument of R21DBYOL (the reference hard-codes (1,1,1,1),
     :268-269) so --model_depth 18/34 means R(2+1)D-18/34 (SURVEY 5.6);
-  * BN+ReLU and BN+residual+ReLU are single kernels; optionally (CSTP_FUSE_BN=1) a BN+ReLU that feeds exactly
-    one convolution is folded into that convolution's gather and never materialised;
+  * BN+ReLU and BN+residual+ReLU are single kernels; the BN+ReLU between a stride-1 spatial convolution and its temporal
+    convolution is folded into the temporal convolution's gather and never materialised (FUSE_BN_TEMPORAL);
   * parameters live in flat HBM arenas (``flatten_parameters``) so EMA / clip / SGD are one
     streaming kernel each instead of ~80 tiny ones (:331-337 rebinding .data per tensor);
   * ``act_dtype="bf16"`` (--act_dtype bf16): bf16 activation STORAGE, as R3DBYOL has it (r3d_byol.py, include/cstp_hip.h
@@ -32,8 +32,6 @@ import torch.nn as nn
 from . import ops
 
 LAYER_SIZES = {1: (1, 1, 1, 1), 18: (2, 2, 2, 2), 34: (3, 4, 6, 3)}
-# Fold BN+ReLU into the consumer convolution's gather (ops.bn_relu_conv3d) instead of materialising it.
-FUSE_BN_INTO_CONV = os.environ.get("CSTP_FUSE_BN", "0") == "1"
 # Default path: the BatchNorm + ReLU between a stride-1 3x3 spatial convolution and its temporal convolution is applied inside
 # the temporal convolution's gather (forward and weight gradient, igemm_k1s / igemm_k2s <.., AFF>) wherever the spatial
 # convolution's kernel left the statistics AND the range of its output (igemm_k1p<MT, true>): the normalised mid-channel
@@ -140,9 +138,8 @@ class _BatchNorm(nn.Module):
     def relu_then(self, conv, x, groups=1, bn_groups=0, bn_pivot=None):
         """conv(relu(self(x))) with this BN's apply+ReLU folded into ``conv``'s gather: only the statistics
         pass touches x before the convolution, and relu(bn(x)) is never written to HBM.  ``bn_groups`` / ``bn_pivot``: the
-        BatchNorm behind ``conv`` (ops.conv3d)."""
-        if not self.training:
-            return conv(self(x, relu=True))
+        BatchNorm behind ``conv`` (ops.conv3d).  Precondition: ``self.training`` -- batch statistics; the caller checks it
+        (SpatioTemporalConv.forward) and materialises this BatchNorm in eval mode."""
         y = ops.bn_relu_conv3d(x, self.weight, self.bias, self.running_mean, self.running_var, conv.weight, conv.stride,
                                conv.padding, groups, True, self.eps, self.momentum, bn_groups, bn_pivot)
         if not getattr(self, "_nbt_in_arena", False):
@@ -219,15 +216,11 @@ class SpatioTemporalConv(nn.Module):
         apply+ReLU precedes this module in the block (bn1 -> relu1 -> conv2, :142-143).  ``out_bn``: the BatchNorm that consumes this
         module's output (bn1 / bn2 / downsamplebn, :142-147): in train mode the temporal convolution leaves its statistics where
         its kernel can.
-        With FUSE_BN_INTO_CONV each BN+ReLU is folded into the following convolution's gather (the normalised
-        tensor is never written: -36 % BN traffic, -7 ms/step of BN kernels, -7 GB of activations at cfg2) --
-        but the per-element affine costs the MFMA kernels' gather more than the two HBM passes it removes
-        (+8 ms/step on MI355X, profiles/r01), so the default materialises BN outputs."""
+        ``pre_bn``'s output is materialised; this module's own BN+ReLU is folded into the temporal convolution's gather where
+        FUSE_BN_TEMPORAL applies and materialised otherwise.  (Folding every BN+ReLU into its consumer's gather was measured
+        slower and removed: DESIGN.md's negative results.)"""
         if x.dtype == torch.bfloat16:
             return self._forward_bf16(x, groups, pre_bn, grad_join)
-        if FUSE_BN_INTO_CONV:
-            x = self.spatial_conv(x) if pre_bn is None else pre_bn.relu_then(self.spatial_conv, x, groups)
-            return self.bn.relu_then(self.temporal_conv, x, groups)
         if pre_bn is not None:
             x = pre_bn(x, relu=True, groups=groups)
         x = self.spatial_conv(x, groups if self.bn.training else 0, self.bn.running_mean, grad_join if pre_bn is None else None)
@@ -241,7 +234,7 @@ class SpatioTemporalConv(nn.Module):
     def _forward_bf16(self, x, groups, pre_bn, grad_join):
         """bf16 storage: spatial conv -> bf16 BN+ReLU, materialised -> temporal conv.  The fp32 path's fusions have no bf16
         kernels and are off here by construction, not by a lookup that happens to fail: no BatchNorm folded into a gather
-        (FUSE_BN_INTO_CONV, FUSE_BN_TEMPORAL / in_affine), no statistics from a convolution's epilogue (bn_groups / bn_pivot)."""
+        (FUSE_BN_TEMPORAL / in_affine), no statistics from a convolution's epilogue (bn_groups / bn_pivot)."""
         if pre_bn is not None:
             x = pre_bn(x, relu=True, groups=groups)
         x = self.spatial_conv(x, grad_join=grad_join if pre_bn is None else None)
@@ -273,8 +266,7 @@ class SpatioTemporalResBlock(nn.Module):
             return self._forward_drop_path(x, groups, scale)
         # the block's input feeds two ops -- conv1 and the residual addition (or, in a downsample block, conv1 and the shortcut
         # convolution): their two gradients are summed inside the second op's kernel instead of by a separate add pass
-        join = ops.GradJoin(2) if (self.training and torch.is_grad_enabled() and x.requires_grad
-                                   and (x.dtype == torch.bfloat16 or not FUSE_BN_INTO_CONV)) else None
+        join = ops.GradJoin(2) if (self.training and torch.is_grad_enabled() and x.requires_grad) else None
         # conv2(relu1(bn1(conv1(x))))
         res = self.conv2(self.conv1(x, groups, grad_join=join, out_bn=self.bn1), groups, pre_bn=self.bn1, out_bn=self.bn2)
         if self.downsample:
@@ -287,8 +279,7 @@ class SpatioTemporalResBlock(nn.Module):
         """relu(x + scale[b] * bn2(res)): bn2 runs without residual and ReLU (its statistics may still come from the convolution's
         epilogue) and ops.drop_path_add_relu joins the branch with x or the shortcut output.  The two gradients of the block's
         input are summed by autograd here; a downsample block keeps the join of its two convolutions."""
-        join = ops.GradJoin(2) if (self.downsample and torch.is_grad_enabled() and x.requires_grad
-                                   and (x.dtype == torch.bfloat16 or not FUSE_BN_INTO_CONV)) else None
+        join = ops.GradJoin(2) if (self.downsample and torch.is_grad_enabled() and x.requires_grad) else None
         res = self.conv2(self.conv1(x, groups, grad_join=join, out_bn=self.bn1), groups, pre_bn=self.bn1, out_bn=self.bn2)
         if self.downsample:
             x = self.downsamplebn(self.downsampleconv(x, groups, grad_join=join, out_bn=self.downsamplebn), groups=groups)

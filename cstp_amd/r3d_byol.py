@@ -32,7 +32,6 @@ implicit-GEMM kernels, the stem the 343-tap / 3-channel case, MaxPool3d has its 
 from __future__ import annotations
 
 import copy
-import os
 
 import torch
 import torch.nn as nn
@@ -49,15 +48,12 @@ def conv3x3x3(in_planes, out_planes, stride=1):
     return Conv3d(in_planes, out_planes, kernel_size=3, stride=stride, padding=1, bias=False)
 
 
-RESIDUAL_JOIN = os.environ.get("CSTP_R3D_JOIN", "1") != "0"      # A/B switch: 0 = autograd's add pass sums the two gradients
-
-
 def _residual_join(block, x):
     """A block's input feeds conv1 AND the residual addition (or the shortcut convolution): in a training forward its two gradients
     are summed inside the ops (ops.GradJoin: the second contributor adds in its kernel's epilogue) instead of by autograd's add pass."""
     # (bf16 storage only: 16 ATen adds per 3D-ResNet-50 step gone, 19.58 -> 19.50 ms; with fp32 storage the accumulating epilogue
     #  costs what the add pass did -- 28.26 vs 28.18 ms -- and the blocks keep autograd's add: profiles/r04/ab_r3d_gradjoin.log)
-    return ops.GradJoin(2) if (RESIDUAL_JOIN and x.dtype == torch.bfloat16 and block.training and torch.is_grad_enabled()
+    return ops.GradJoin(2) if (x.dtype == torch.bfloat16 and block.training and torch.is_grad_enabled()
                                and x.requires_grad) else None
 
 

@@ -28,8 +28,8 @@
  *         gradients), likewise process-wide;
  *       * the per-thread pack mode and record list (cstp_pack_mode), the process-wide set of registered workspaces
  *         (cstp_pack_register) and the records last drained for each (cstp_pack_recorded; both mutex-guarded);
- *       * environment knobs read once: CSTP_GEMM, CSTP_DETERMINISTIC, CSTP_PERSIST_CUS, CSTP_K1P_QUAD, CSTP_K1W, CSTP_LINEAR,
- *         CSTP_BN_SMALL, CSTP_TILE / CSTP_WTILE (developer overrides).
+ *       * environment knobs read once: CSTP_GEMM, CSTP_DETERMINISTIC, CSTP_PERSIST_CUS, CSTP_TILE / CSTP_WTILE (developer
+ *         overrides).
  *     A caller that wants two arithmetics side by side in one process must serialise the switch with its launches
  *     (bench.py does, between timed loops); results never depend on the state of another STREAM.
  */
@@ -78,7 +78,7 @@ const char* cstp_last_error(void);
 /* ---- convolution (F.conv3d / F.linear and their autograd) ------------------------------- */
 /* (F.linear is the D = H = W = 1, 1x1x1 case.  On n <= 32 rows -- the heads, r21d_byol.py:159-176, 318-334 -- forward, data gradient
  *  (reduction length a multiple of 64) and weight gradient run as weight-streaming kernels in EXACT fp32 FMAs, slices summed in a
- *  fixed order (csrc/linear.h); CSTP_LINEAR=0, the native-f32 arithmetic and a pinned tile keep them on the convolution kernels.) */
+ *  fixed order (csrc/linear.h); the native-f32 arithmetic and a pinned tile keep them on the convolution kernels.) */
 size_t cstp_conv3d_workspace_bytes(const cstp_conv_desc* desc);
 /* y[n][k][do][ho][wo] = conv3d(T(x), w) (+ bias[k] when bias != NULL).  w is [k][c][kt][kh][kw].
  * T = identity when in_affine == NULL, else the fused BN(+ReLU) input transform above.  (The _am variants: with an in_affine the
@@ -269,7 +269,10 @@ int cstp_bn_stats_train(void* stream, const float* x, const float* gamma, const 
                         int32_t c, int32_t s, int32_t groups, float eps, float momentum, void* ws, size_t ws_bytes);
 /* Backward of the fused op.  y is the forward OUTPUT (its sign is the ReLU mask); when the output was
  * never materialised (cstp_bn_stats_train + cstp_in_affine) pass y = NULL and the scale_shift table and the
- * mask is recomputed from x.  dresidual may be NULL.  dgamma/dbeta: [c], summed over the groups. */
+ * mask is recomputed from x.  dresidual may be NULL.  dgamma/dbeta: [c], summed over the groups.
+ * s > 1 only: a BatchNorm1d backward (s = 1) is REFUSED with an error that names cstp_bn1d_backward, here and in
+ * cstp_bn_backward_am.  The fp32 forms these entries once ran for s = 1 missed the project's tolerance on few rows per group
+ * (see cstp_bn1d_backward); an entry that says where to go is better than one that silently answers outside it. */
 int cstp_bn_backward(void* stream, const float* x, const float* y, const float* dy, const float* gamma,
                      const float* save_mean, const float* save_invstd, const float* scale_shift, float* dx,
                      float* dresidual, float* dgamma, float* dbeta, int32_t n, int32_t c, int32_t s, int32_t groups,
@@ -286,7 +289,8 @@ int cstp_bn_backward_am(void* stream, const float* x, const float* y, const floa
 /* BatchNorm1d (x [n][c], s = 1) backward with the batch statistics REBUILT from x and eps in fp64 and dx formed in fp64: with
  * few rows per group dx is eps / (var + eps) of the size of the terms it is the difference of (two rows: exactly that, in
  * every feature), which an fp32 invstd cannot carry.  No saved statistics, no workspace; y (the forward output) is needed only
- * with relu; dresidual may be NULL; accumulate as in cstp_bn_backward_am.  cstp_bn_backward with s = 1 remains (fp32 forms). */
+ * with relu; dresidual may be NULL; accumulate as in cstp_bn_backward_am.  The only backward for s = 1: cstp_bn_backward[_am]
+ * refuse it. */
 int cstp_bn1d_backward(void* stream, const float* x, const float* y, const float* dy, const float* gamma, float* dx,
                        float* dresidual, float* dgamma, float* dbeta, int32_t n, int32_t c, int32_t groups, float eps,
                        int32_t relu, int32_t accumulate);

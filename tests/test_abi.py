@@ -75,6 +75,11 @@ def test_every_bn_entry_point_fails_cleanly_on_its_early_return_path():
         ("cstp_bn_stats_train", (None, one, one, one, None, None, one, one, one, 4, 8, 1, 1, f(1e-5), f(0.1), one, 1 << 20), b"bad shape"),
         ("cstp_bn_stats_train", (None, one, one, one, one, None, one, one, one, 4, 8, 16, 1, f(1e-5), f(0.1), one, 1 << 20),
          b"running stats must come as a pair"),
+        # [B][F] tensors (s = 1): refused with the name of the entry point that serves them, not launched
+        ("cstp_bn_backward_am", (None, one, one, one, one, one, one, one, one, one, one, one, 4, 8, 1, 1, 0, one, 1 << 20, None, 0),
+         b"cstp_bn1d_backward"),
+        ("cstp_bn_backward", (None, one, one, one, one, one, one, one, one, one, one, one, 4, 8, 1, 1, 0, one, 1 << 20),
+         b"cstp_bn1d_backward"),
     ]
     for name, args, needle in calls:
         rc = getattr(lib, name)(*args)

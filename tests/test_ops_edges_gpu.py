@@ -230,8 +230,8 @@ def test_bn1d_two_values_per_channel(shape, groups):
         dx1 = -dx2 = gamma invstd (g1 - g2) / 2 * (1 - h^2) = gamma invstd (g1 - g2) / 2 * eps / (var + eps),
     the difference of two terms that agree to eps / var = 1e-5 .. 1e-4 of their size in EVERY channel, so the global metric has
     no large channel to hide behind.  An fp32 evaluation keeps 2^-24 / (eps / var) = 1e-3 .. 1e-2 of that difference whatever
-    the order of its operations, and so does any evaluation from an invstd saved in fp32: the fp32 backward
-    (bn1d_bwd_kernel) measured 1.7e-3 .. 2.7e-3 here against the bar 1e-4, stock PyTorch fp32 on the CPU 9.3e-4.  ops routes
+    the order of its operations, and so does any evaluation from an invstd saved in fp32: the former fp32 backward
+    measured 1.7e-3 .. 2.7e-3 here against the bar 1e-4, stock PyTorch fp32 on the CPU 9.3e-4.  ops routes
     BatchNorm1d's backward to cstp_bn1d_backward, which rebuilds the statistics from x and eps and forms dx in fp64."""
     x, gamma, beta, res, rm, rv, dy = _bn_tensors(shape, 62 + shape[1])
     fails = []
