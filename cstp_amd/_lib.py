@@ -204,6 +204,11 @@ SIGNATURES = {
     "cstp_probe_step": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P,
                                   c_size_t]),
     "cstp_probe_predict": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P]),
+    # NT-Xent with a queue of extra negatives (csrc/ntxq.h)
+    "cstp_ntxq_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "cstp_ntxq_forward": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_float, _P, c_size_t]),
+    "cstp_ntxq_backward": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_float, _P, c_size_t]),
+    "cstp_ntxq_push": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32]),
 }
 
 _lib = None

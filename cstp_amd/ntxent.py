@@ -8,6 +8,12 @@ process group and ``gather=True`` the local [B_local, F] embeddings are gathered
 [B_global, F] first.  The gather carries gradient only for this rank's slice (every rank
 evaluates the identical global loss), so the caller multiplies the loss by world_size to
 undo DDP's gradient averaging -- ``ddp_scale`` holds that factor.
+
+``queue_size=K`` (--ntxent_queue K, default 0 = exactly the loss above) adds a FIFO queue of K past embeddings as extra negatives
+of every row (MoCo, He et al. 2020; NNCLR, Dwibedi et al. 2021): what it holds are past ONLINE projections, L2-normalised, the
+all-gathered rows of each step in push order, so every rank holds the same queue without any communication.  The queue is a
+constant of the loss (no gradient reaches it) and is NOT checkpointed: a resumed run starts with an empty queue and has refilled
+it after K / (2 * batch_size) steps; checkpoint keys and the wire format are unchanged.
 """
 from __future__ import annotations
 
@@ -58,15 +64,50 @@ class _PutLocal(torch.autograd.Function):
         return None, g[ctx.off:ctx.off + ctx.b], None
 
 
+class _AfterBackward(torch.autograd.Function):
+    """Identity on ``x``; ``fn()`` runs once the gradient of everything computed from the result has arrived, i.e. after the
+    backward pass of the loss that read the queue."""
+
+    @staticmethod
+    def forward(ctx, x, fn):
+        ctx.fn = fn
+        return x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        ctx.fn()
+        return g, None
+
+
 class NTXentLoss(torch.nn.Module):
-    def __init__(self, device, batch_size, temperature, use_cosine_similarity=True, gather=True, kernel=None):
+    def __init__(self, device, batch_size, temperature, use_cosine_similarity=True, gather=True, kernel=None, queue_size=0,
+                 queue_kernel=None, push_kernel=None):
         """``kernel(reps [2N, F], temperature) -> scalar``: the HIP NT-Xent kernels by default (ops.ntxent); injectable so
-        that the gather / scale logic can be driven on CPU (tests/test_dist_gloo.py)."""
+        that the gather / scale logic can be driven on CPU (tests/test_dist_gloo.py).
+
+        ``queue_size`` K > 0: the loss is ``queue_kernel(reps, queue [K, F], n_valid, temperature)`` (ops.ntxent_queue) and
+        every step ends with ``push_kernel(reps.detach(), queue, ptr)`` (ops.ntxent_queue_push: the 2 * batch_size gathered rows,
+        normalised, to rows [ptr, ptr + 2 * batch_size)); both injectable for the same reason.  The buffer is allocated at the
+        first call, on the embeddings' device; ``ptr`` and ``n_valid`` are host integers, nothing is read back from the device.
+        The loss sees the queue as it stood before its own step's push.  The backward pass re-reads the queue, so where a
+        gradient is wanted the push runs at the end of that backward pass (one ``backward()`` per ``forward()``, as
+        PretrainStep does); without one (no_grad, or embeddings that need no gradient) it runs right after the loss.
+        K must be a positive multiple of 2 * batch_size: a push never wraps.  Not checkpointed (module docstring)."""
         super().__init__()
         self._kernel = kernel if kernel is not None else ops.ntxent
         if not use_cosine_similarity:
             raise NotImplementedError("the CSTP driver only builds the cosine-similarity variant (main_byol.py:195)")
         self.batch_size, self.temperature, self.device, self.gather = batch_size, temperature, device, gather
+        if isinstance(queue_size, bool) or not isinstance(queue_size, int) or queue_size < 0:
+            raise ValueError("--ntxent_queue takes 0 (off) or a positive number of rows, got %r" % (queue_size,))
+        if queue_size % (2 * batch_size) != 0:
+            raise ValueError("--ntxent_queue %d must be a multiple of 2 * batch_size = %d: a step pushes that many rows and a "
+                             "push never wraps" % (queue_size, 2 * batch_size))
+        self.queue_size = queue_size
+        if queue_size > 0:
+            self._queue_kernel = queue_kernel if queue_kernel is not None else ops.ntxent_queue
+            self._push_kernel = push_kernel if push_kernel is not None else ops.ntxent_queue_push
+            self.queue, self.ptr, self.n_valid = None, 0, 0
 
     @property
     def ddp_scale(self) -> float:
@@ -81,4 +122,22 @@ class NTXentLoss(torch.nn.Module):
             # the reference fails here too: its mask is built for 2*batch_size rows (NTXent.py:23-29,57)
             raise RuntimeError("NTXentLoss was built for batch_size=%d but got %d embeddings"
                                % (self.batch_size, zis.shape[0]))
-        return self._kernel(torch.cat([zjs, zis], dim=0), self.temperature)
+        reps = torch.cat([zjs, zis], dim=0)
+        if self.queue_size == 0:
+            return self._kernel(reps, self.temperature)
+        if self.queue is None:
+            self.queue = torch.zeros((self.queue_size, reps.shape[1]), dtype=torch.float32, device=reps.device)
+        rows = reps.detach()
+
+        def push():
+            self._push_kernel(rows, self.queue, self.ptr)
+            self.ptr = (self.ptr + rows.shape[0]) % self.queue_size
+            self.n_valid = min(self.n_valid + rows.shape[0], self.queue_size)
+
+        deferred = torch.is_grad_enabled() and reps.requires_grad
+        if deferred:
+            reps = _AfterBackward.apply(reps, push)
+        loss = self._queue_kernel(reps, self.queue, self.n_valid, self.temperature)
+        if not deferred:
+            push()
+        return loss

@@ -1980,6 +1980,89 @@ def ntxent(reps, temperature):
     return _NTXent.apply(reps, float(temperature))
 
 
+NTXQ_MAX_F = 2048
+
+
+class _NTXentQueue(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, reps, queue, n_valid, temperature):
+        lib = _lib.load()
+        two_n, f = reps.shape
+        cap = queue.shape[0]
+        nbytes = lib.cstp_ntxq_workspace_bytes(two_n, f, n_valid)
+        if nbytes == 0:
+            raise _lib.CstpError("ntxent_queue: unsupported shape reps [%d, %d], n_valid %d (rows even in 4..8192, features in "
+                                 "1..%d)" % (two_n, f, n_valid, NTXQ_MAX_F))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=reps.device)  # private: lives until backward
+        loss = torch.empty(1, dtype=torch.float32, device=reps.device)
+        check(lib.cstp_ntxq_forward(_stream(), reps.data_ptr(), queue.data_ptr(), loss.data_ptr(), two_n, f, cap, n_valid,
+                                    temperature, ws.data_ptr(), ws.numel()), "cstp_ntxq_forward")
+        ctx.save_for_backward(reps, queue, ws)
+        ctx.n_valid, ctx.temperature = n_valid, temperature
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, dloss):
+        lib = _lib.load()
+        reps, queue, ws = ctx.saved_tensors
+        dloss = _req(dloss.reshape(1), "ntxent_queue grad_output")
+        dreps = torch.empty_like(reps)
+        check(lib.cstp_ntxq_backward(_stream(), reps.data_ptr(), queue.data_ptr(), dloss.data_ptr(), dreps.data_ptr(),
+                                     reps.shape[0], reps.shape[1], queue.shape[0], ctx.n_valid, ctx.temperature, ws.data_ptr(),
+                                     ws.numel()), "cstp_ntxq_backward")
+        return dreps, None, None, None
+
+
+def _ntxq_operands(what, reps, queue):
+    for t, name in ((reps, "%s representations" % what), (queue, "%s queue" % what)):
+        if not t.is_cuda:
+            raise _lib.CstpError("%s must be on a HIP device (cstp_amd has no CPU path)" % name)
+        if t.dtype != torch.float32:
+            raise _lib.CstpError("%s must be float32, got %s" % (name, t.dtype))
+        if t.dim() != 2:
+            raise _lib.CstpError("%s must be [rows, features], got %s" % (name, tuple(t.shape)))
+        if not t.is_contiguous():
+            raise _lib.CstpError("%s must be contiguous" % name)
+    if reps.shape[1] != queue.shape[1]:
+        raise _lib.CstpError("%s: the representations have %d features, the queue %d" % (what, reps.shape[1], queue.shape[1]))
+    if reps.device != queue.device:
+        raise _lib.CstpError("%s: the representations are on %s, the queue on %s" % (what, reps.device, queue.device))
+
+
+def ntxent_queue(reps, queue, n_valid, temperature):
+    """NT-Xent over reps = cat(zjs, zis) [2N, F] with rows [0, n_valid) of ``queue`` [cap, F] as extra negatives of every row
+    (include/cstp_hip.h: cstp_ntxq_forward).  The queue's rows are constants of unit length (ntxent_queue_push writes them): no
+    gradient reaches it, neither pass writes it and rows from n_valid on are not read.  The [2N, n_valid] score matrix is never
+    built (csrc/ntxq.h).  n_valid == 0 IS ``ntxent(reps, temperature)``: the same call, the same bits."""
+    _ntxq_operands("ntxent_queue", reps, queue)
+    if isinstance(n_valid, bool) or not isinstance(n_valid, int) or not 0 <= n_valid <= queue.shape[0]:
+        raise _lib.CstpError("ntxent_queue: n_valid must be an int in [0, %d], got %r" % (queue.shape[0], n_valid))
+    if n_valid == 0:
+        return ntxent(reps, temperature)
+    return _NTXentQueue.apply(reps, queue, n_valid, float(temperature))
+
+
+def ntxent_queue_splits(two_n, f, n_valid):
+    """Blocks along the queue per 64-row tile that ntxent_queue uses for these sizes (0 for an empty queue), read off the
+    workspace size: cstp_ntxq_workspace_bytes = the in-batch block + nsplit * two_n * (2 + f) floats."""
+    lib = _lib.load()
+    total, base = lib.cstp_ntxq_workspace_bytes(two_n, f, n_valid), lib.cstp_ntxent_workspace_bytes(two_n, f)
+    if total == 0:
+        raise _lib.CstpError("ntxent_queue_splits: unsupported sizes (%d, %d, %d)" % (two_n, f, n_valid))
+    return (total - base) // (two_n * (2 + f) * 4)
+
+
+def ntxent_queue_push(reps, queue, ptr):
+    """queue[ptr + i] <- reps[i] / max(|reps[i]|, 1e-8) for every row of reps [R, F] (cstp_ntxq_push); ptr + R <= cap is the
+    caller's to guarantee (NTXentLoss keeps cap a multiple of R).  One launch on the current stream; no autograd."""
+    _ntxq_operands("ntxent_queue_push", reps, queue)
+    r, cap = reps.shape[0], queue.shape[0]
+    if isinstance(ptr, bool) or not isinstance(ptr, int) or ptr < 0 or ptr + r > cap:
+        raise _lib.CstpError("ntxent_queue_push: rows [%r, %r + %d) do not lie inside a queue of %d rows" % (ptr, ptr, r, cap))
+    lib = _lib.load()
+    check(lib.cstp_ntxq_push(_stream(), reps.detach().data_ptr(), queue.data_ptr(), r, reps.shape[1], cap, ptr), "cstp_ntxq_push")
+
+
 SIM_TOPK_MAX_K = 64
 
 

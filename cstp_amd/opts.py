@@ -5,6 +5,11 @@ scripts -- README.md:41-50, script/r2p1d/kin400/*.sh -- run unchanged), expresse
 Additions (all optional, defaults reproduce the reference):
   --ntxent_weight   weight of the NT-Xent term on all-gathered projector embeddings (default 0:
                     the reference builds the criterion but never adds it, main_byol.py:71-73,191-197)
+  --ntxent_queue    K rows of extra negatives for that term (default 0 = off, today's loss): a FIFO queue of past ONLINE projections,
+                    L2-normalised, the all-gathered rows of every step in push order -- identical on every rank without any
+                    communication -- read by the streaming kernels of csrc/ntxq.h (no [2N, K] matrix is built).  K must be a
+                    multiple of 2 * batch_size; needs --ntxent_weight != 0.  The queue is NOT checkpointed: a resumed run refills
+                    it in K / (2 * batch_size) steps (cstp_amd/ntxent.py; every driver but main_byol.py ignores the flag)
   --synthetic_len   samples per epoch of the built-in synthetic dataset (--dataset synthetic)
   --max_steps       stop an epoch after this many iterations (0 = full epoch)
   --bucket_cap_mb   DDP gradient bucket size (xGMI ring all-reduce is per-link bound)
@@ -119,6 +124,8 @@ _FLAGS = [
     ("lmdb_path", "", str, "LMDB path"),
     # additions
     ("ntxent_weight", 0.0, float, "weight of the NT-Xent term on all-gathered embeddings (0 = reference)"),
+    ("ntxent_queue", 0, int, "main_byol.py: rows of the NT-Xent term's queue of past online projections used as extra negatives "
+     "(0 = off; a multiple of 2 * batch_size; needs --ntxent_weight; not checkpointed)"),
     ("synthetic_len", 256, int, "samples per epoch for --dataset synthetic"),
     ("max_steps", 0, int, "stop each epoch after this many iterations (0 = all)"),
     ("bucket_cap_mb", 25, int, "DDP gradient bucket size in MB"),

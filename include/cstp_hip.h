@@ -740,6 +740,38 @@ int cstp_droppath_add_relu_forward(void* stream, const void* z, const void* res,
 int cstp_droppath_add_relu_backward(void* stream, const void* y, const void* dy, const float* scale, void* dz, void* dres,
                                     int64_t n, int64_t row, int32_t bf16);
 
+/* ---- NT-Xent with a queue of extra negatives (csrc/ntxq.h, included from csrc/retrieve.hip) ----------
+ * reps [R][f] fp32 = cat(zjs, zis) as for cstp_ntxent_*; queue [cap][f] fp32, constant rows of UNIT LENGTH (cstp_ntxq_push
+ * writes them), of which rows [0, n_valid) count; T = temperature.  With the reference's cosine
+ *   s_ij = <r_i, r_j> / max(|r_i| |r_j|, 1e-8),   c_ik = <r_i, queue_k> / max(|r_i|, 1e-8)   (|queue_k| is taken as 1)
+ *   loss = 1/R sum_i [ -s_{i,(i + R/2) mod R} / T + log( sum_{j != i} exp(s_ij / T) + sum_{k < n_valid} exp(c_ik / T) ) ]
+ * n_valid == 0 is cstp_ntxent_forward's loss.  The gradient reaches reps only: the queue is never written by forward or backward,
+ * and rows from n_valid on are never read (they may hold anything, NaN included).
+ * A dot product is one fp32 fmaf chain in ascending feature order on v_mfma_f32_32x32x2_f32 (cstp_simtopk's walk: 64 rows x
+ * tiles of 128 queue rows), so a score does not depend on the tile or the split that computes it; the [R][n_valid] matrix
+ * never exists.  Forward keeps a running (max, sum exp) per row and split and folds them, in split order, with the in-batch
+ * row; the maximum is subtracted throughout, so 1/T = 100 is safe.  Backward recomputes the scores tile by tile, forms
+ * p_ik = exp(c_ik / T - lse_i) and accumulates P x queue in registers per slice of 256 features; the partial [split][R][f]
+ * sums are added in split order to the in-batch gradient (cstp_ntxent_backward's arithmetic with the new lse) through the
+ * derivative of the normalisation, scaled by dloss / (R T).  No atomics: equal inputs give equal bits.
+ * The workspace of forward must reach backward unchanged.  cstp_ntxq_workspace_bytes is a pure host function (0 on bad
+ * arguments): cstp_ntxent_workspace_bytes(R, f) + nsplit * R * (2 + f) * 4, where
+ *   nsplit = 0 for n_valid == 0, else max(1, min(256 / ceil(R / 64), ceil(n_valid / 128) / 2, 2^22 / (R f))), then
+ *   rounded so that no split is empty -- the partial gradients take 16 MiB at the most, or one split.
+ * Launches: forward 3 + 1 (+ 1 with a non-empty queue), backward 2 (+ 2).
+ * Limits, refused with a message before any HIP call: a null pointer; R odd, < 4 or > 8192; f outside 1..2048; T <= 0;
+ * cap outside [0, 2^30]; n_valid outside [0, cap]; ws smaller than cstp_ntxq_workspace_bytes(R, f, n_valid).
+ *
+ * cstp_ntxq_push: queue[ptr + i] = reps[i] / max(|reps[i]|, 1e-8) for i < R (a zero row is written as zeros); every other row
+ * is left as it is.  One launch; run it after the loss's launches on the same stream.  Refused: a null pointer, R outside
+ * 1..8192, f outside 1..2048, ptr < 0 or ptr + R > cap. */
+size_t cstp_ntxq_workspace_bytes(int32_t R, int32_t f, int32_t n_valid);
+int cstp_ntxq_forward(void* stream, const float* reps, const float* queue, float* loss, int32_t R, int32_t f, int32_t cap,
+                      int32_t n_valid, float temperature, void* ws, size_t ws_bytes);
+int cstp_ntxq_backward(void* stream, const float* reps, const float* queue, const float* dloss, float* dreps, int32_t R,
+                       int32_t f, int32_t cap, int32_t n_valid, float temperature, void* ws, size_t ws_bytes);
+int cstp_ntxq_push(void* stream, const float* reps, float* queue, int32_t R, int32_t f, int32_t cap, int32_t ptr);
+
 #ifdef __cplusplus
 }
 #endif

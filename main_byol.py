@@ -23,6 +23,8 @@ after the JPEG decode on the GPU (cstp_amd.frame_folder); the LMDB data sets are
 New: --knn_every E (default 0 = off) fills the ``acc`` column of the epoch log, which the reference leaves empty: after every E-th
 epoch and after the last one rank 0 classifies labelled test videos by weighted k-NN on the ONLINE encoder (cstp_amd.knn, --knn_k,
 --knn_t) under model.eval() + no_grad, the other ranks wait in a barrier, and training goes on unchanged (KnnMonitor).
+New: --ntxent_queue K (default 0 = off) gives the NT-Xent term (--ntxent_weight) K extra negatives per row: a FIFO queue of past
+online projections, normalised, identical on every rank, not checkpointed (cstp_amd.ntxent, csrc/ntxq.h).
 """
 from __future__ import annotations
 
@@ -81,6 +83,18 @@ def check_knn_opts(opts):
     except ValueError:
         raise ValueError("--knn_every %d with --sample_size %d: the monitor reads whole videos as the video test does, and its "
                          "ClipScale serves --sample_size 112 and 224 only" % (every, opts.sample_size)) from None
+
+
+def check_ntxent_queue_opts(opts):
+    """Refuses a --ntxent_queue the NT-Xent term cannot use; called before any device work.  0 = off: nothing to check."""
+    k = getattr(opts, "ntxent_queue", 0)
+    if k < 0:
+        raise ValueError("--ntxent_queue takes 0 (off) or a positive number of rows, got %d" % k)
+    if k > 0 and opts.ntxent_weight == 0.0:
+        raise ValueError("--ntxent_queue %d with --ntxent_weight 0: the queue feeds a term that is switched off" % k)
+    if k % (2 * opts.batch_size) != 0:
+        raise ValueError("--ntxent_queue %d must be a multiple of 2 * batch_size = %d: a step pushes that many rows and a push "
+                         "never wraps" % (k, 2 * opts.batch_size))
 
 
 class KnnMonitor:
@@ -189,8 +203,9 @@ def main_worker(local_rank, opts):
     print(opts)
     opts.arch = "{}-{}".format(opts.model_name, opts.model_depth)
 
+    check_ntxent_queue_opts(opts)
     criterion_ctr = NTXentLoss(device=local_rank, batch_size=opts.batch_size, temperature=opts.temperature,
-                               use_cosine_similarity=True)
+                               use_cosine_similarity=True, queue_size=getattr(opts, "ntxent_queue", 0))
     train_data = build_dataset(opts)
     print("Length of training data = ", len(train_data))
     per_rank = int(opts.batch_size / opts.world_size)
@@ -255,6 +270,7 @@ def main_worker(local_rank, opts):
 
 def main(opts):
     check_knn_opts(opts)
+    check_ntxent_queue_opts(opts)
     torch.manual_seed(opts.manual_seed)
     np.random.seed(opts.manual_seed)
     random.seed(opts.manual_seed)
