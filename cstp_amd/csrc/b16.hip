@@ -29,16 +29,14 @@
 
 #include "common.h"
 #include "pack_b16.h"
+#include "pool.h"
 
 namespace cstp {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2v __attribute__((ext_vector_type(2)));
 typedef unsigned short u16;
 
-__device__ __forceinline__ float bf2f(u16 v) { return __builtin_bit_cast(float, (unsigned)v << 16); }
 __device__ __forceinline__ float bflo(unsigned v) { return __builtin_bit_cast(float, v << 16); }
 __device__ __forceinline__ float bfhi(unsigned v) { return __builtin_bit_cast(float, v & 0xffff0000u); }
 // two fp32 -> packed bf16 pair (element 0 in the low half), round to nearest even (v_cvt_pk_bf16_f32)
@@ -46,7 +44,6 @@ __device__ __forceinline__ unsigned pack_bf2(float a, float b) {
   f32x2v v = {a, b};
   return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
 }
-__device__ __forceinline__ u16 f2bf(float a) { return (u16)(pack_bf2(a, 0.f) & 0xffffu); }
 
 typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint4 ld16_last(const u16* p) {          // streaming (last-use) 16-byte load
@@ -1131,84 +1128,6 @@ b16_bn_small_bwd_kernel(const u16* __restrict__ x, const u16* __restrict__ y, co
   }
 }
 
-// ---- pooling ------------------------------------------------------------------------------------------------------------------
-// MaxPool3d (models/BE/r3d_byol.py:158): as maxpool3d_fwd/bwd_kernel of misc.hip on bf16 values (comparisons are exact)
-__global__ void b16_maxpool3d_fwd_kernel(const u16* __restrict__ x, u16* __restrict__ y, int32_t* __restrict__ idx, int rows, int D, int H,
-                                         int W, int Do, int Ho, int Wo, int kd, int kh, int kw, int sd, int sh, int sw, int pd, int ph,
-                                         int pw) {
-  const size_t total = (size_t)rows * Do * Ho * Wo;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    size_t r = i;
-    const int wo = (int)(r % Wo); r /= Wo;
-    const int ho = (int)(r % Ho); r /= Ho;
-    const int dd = (int)(r % Do); const size_t row = r / Do;
-    const u16* xp = x + row * (size_t)D * H * W;
-    float best = -INFINITY;
-    u16 bb = 0xff80;     // -inf
-    int bi = -1;
-    for (int a = 0; a < kd; ++a) {
-      const int id = dd * sd - pd + a;
-      if ((unsigned)id >= (unsigned)D) continue;
-      for (int b = 0; b < kh; ++b) {
-        const int ih = ho * sh - ph + b;
-        if ((unsigned)ih >= (unsigned)H) continue;
-        for (int c = 0; c < kw; ++c) {
-          const int iw = wo * sw - pw + c;
-          if ((unsigned)iw >= (unsigned)W) continue;
-          const int fi = (id * H + ih) * W + iw;
-          const u16 raw = xp[fi];
-          const float v = bf2f(raw);
-          if (v > best || v != v || bi < 0) { best = v; bb = raw; bi = fi; }
-        }
-      }
-    }
-    y[i] = bb;
-    idx[i] = bi;
-  }
-}
-
-__global__ void b16_maxpool3d_bwd_kernel(const u16* __restrict__ dy, const int32_t* __restrict__ idx, u16* __restrict__ dx, int rows, int D,
-                                         int H, int W, int Do, int Ho, int Wo, int kd, int kh, int kw, int sd, int sh, int sw, int pd,
-                                         int ph, int pw) {
-  const size_t total = (size_t)rows * D * H * W;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-    size_t r = i;
-    const int w = (int)(r % W); r /= W;
-    const int h = (int)(r % H); r /= H;
-    const int d = (int)(r % D); const size_t row = r / D;
-    const int fi = (d * H + h) * W + w;
-    const int d_lo = (d + pd - kd + sd) > 0 ? (d + pd - kd + sd) / sd : 0, d_hi = (d + pd) / sd < Do - 1 ? (d + pd) / sd : Do - 1;
-    const int h_lo = (h + ph - kh + sh) > 0 ? (h + ph - kh + sh) / sh : 0, h_hi = (h + ph) / sh < Ho - 1 ? (h + ph) / sh : Ho - 1;
-    const int w_lo = (w + pw - kw + sw) > 0 ? (w + pw - kw + sw) / sw : 0, w_hi = (w + pw) / sw < Wo - 1 ? (w + pw) / sw : Wo - 1;
-    const size_t obase = row * (size_t)Do * Ho * Wo;
-    float acc = 0.f;
-    for (int a = d_lo; a <= d_hi; ++a)
-      for (int b = h_lo; b <= h_hi; ++b)
-        for (int c = w_lo; c <= w_hi; ++c) {
-          const size_t o = obase + ((size_t)a * Ho + b) * Wo + c;
-          if (idx[o] == fi) acc += bf2f(dy[o]);
-        }
-    dx[i] = f2bf(acc);
-  }
-}
-
-// AdaptiveAvgPool3d(1): bf16 rows -> fp32 means (one wave per row); backward fp32 dy -> bf16 dx
-__global__ void b16_avgpool_fwd_kernel(const u16* __restrict__ x, float* __restrict__ y, int rows, int s) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= rows) return;
-  const u16* p = x + (size_t)row * s;
-  float a = 0.f;
-  for (int i = lane; i < s; i += 64) a += bf2f(p[i]);
-  a = wave_sum(a);
-  if (lane == 0) y[row] = a / (float)s;
-}
-
-__global__ void b16_avgpool_bwd_kernel(const float* __restrict__ dy, u16* __restrict__ dx, int rows, int s) {
-  const size_t total = (size_t)rows * s;
-  const float inv = 1.f / (float)s;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) dx[i] = f2bf(dy[i / s] * inv);
-}
-
 }  // namespace cstp
 
 using namespace cstp;
@@ -1630,51 +1549,28 @@ extern "C" int cstp_b16_bn_forward_eval(void* stream, const uint16_t* x, const u
   return 0;
 }
 
-// ---- pooling ------------------------------------------------------------------------------------------------------------------
-static bool b16_pool_dims(int D, int H, int W, const int32_t* k, const int32_t* st, const int32_t* pd, int& Do, int& Ho, int& Wo) {
-  for (int i = 0; i < 3; ++i)
-    if (k[i] <= 0 || st[i] <= 0 || pd[i] < 0 || 2 * pd[i] > k[i]) return false;
-  Do = (D + 2 * pd[0] - k[0]) / st[0] + 1;
-  Ho = (H + 2 * pd[1] - k[1]) / st[1] + 1;
-  Wo = (W + 2 * pd[2] - k[2]) / st[2] + 1;
-  return Do > 0 && Ho > 0 && Wo > 0;
-}
+// ---- pooling (pool.h) ---------------------------------------------------------------------------------------------------------
+// the bf16 grid rule (pool.h: PoolBlocks)
+static unsigned b16_pool_blocks(size_t n) { return b16_grid(n, 256); }
 
 extern "C" int cstp_b16_maxpool3d_forward(void* stream, const uint16_t* x, uint16_t* y, int32_t* argmax, int32_t rows, int32_t d, int32_t h,
                                           int32_t w, const int32_t* kernel3, const int32_t* stride3, const int32_t* pad3) {
   CSTP_REQUIRE(x && y && argmax && kernel3 && stride3 && pad3 && rows > 0 && d > 0 && h > 0 && w > 0, "bad argument");
-  int Do, Ho, Wo;
-  CSTP_REQUIRE(b16_pool_dims(d, h, w, kernel3, stride3, pad3, Do, Ho, Wo), "bad pooling geometry");
-  CSTP_REQUIRE((size_t)d * h * w < (1ull << 31), "plane too large for int32 argmax");
-  const size_t total = (size_t)rows * Do * Ho * Wo;
-  hipLaunchKernelGGL(b16_maxpool3d_fwd_kernel, dim3(b16_grid(total, 256)), dim3(256), 0, as_stream(stream), x, y, argmax, rows, d, h, w, Do,
-                     Ho, Wo, kernel3[0], kernel3[1], kernel3[2], stride3[0], stride3[1], stride3[2], pad3[0], pad3[1], pad3[2]);
-  CSTP_LAUNCH_CHECK();
-  return 0;
+  return maxpool3d_forward(stream, b16_pool_blocks, x, y, argmax, rows, d, h, w, kernel3, stride3, pad3);
 }
 
 extern "C" int cstp_b16_maxpool3d_backward(void* stream, const uint16_t* dy, const int32_t* argmax, uint16_t* dx, int32_t rows, int32_t d,
                                            int32_t h, int32_t w, const int32_t* kernel3, const int32_t* stride3, const int32_t* pad3) {
   CSTP_REQUIRE(dy && argmax && dx && kernel3 && stride3 && pad3 && rows > 0 && d > 0 && h > 0 && w > 0, "bad argument");
-  int Do, Ho, Wo;
-  CSTP_REQUIRE(b16_pool_dims(d, h, w, kernel3, stride3, pad3, Do, Ho, Wo), "bad pooling geometry");
-  const size_t total = (size_t)rows * d * h * w;
-  hipLaunchKernelGGL(b16_maxpool3d_bwd_kernel, dim3(b16_grid(total, 256)), dim3(256), 0, as_stream(stream), dy, argmax, dx, rows, d, h, w, Do,
-                     Ho, Wo, kernel3[0], kernel3[1], kernel3[2], stride3[0], stride3[1], stride3[2], pad3[0], pad3[1], pad3[2]);
-  CSTP_LAUNCH_CHECK();
-  return 0;
+  return maxpool3d_backward(stream, b16_pool_blocks, dy, argmax, dx, rows, d, h, w, kernel3, stride3, pad3);
 }
 
 extern "C" int cstp_b16_avgpool_forward(void* stream, const uint16_t* x, float* y, int32_t rows, int32_t s) {
   CSTP_REQUIRE(x && y && rows > 0 && s > 0, "bad argument");
-  hipLaunchKernelGGL(b16_avgpool_fwd_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, as_stream(stream), x, y, rows, s);
-  CSTP_LAUNCH_CHECK();
-  return 0;
+  return avgpool_forward(stream, x, y, rows, s);
 }
 
 extern "C" int cstp_b16_avgpool_backward(void* stream, const float* dy, uint16_t* dx, int32_t rows, int32_t s) {
   CSTP_REQUIRE(dy && dx && rows > 0 && s > 0, "bad argument");
-  hipLaunchKernelGGL(b16_avgpool_bwd_kernel, dim3(b16_grid((size_t)rows * s, 256)), dim3(256), 0, as_stream(stream), dy, dx, rows, s);
-  CSTP_LAUNCH_CHECK();
-  return 0;
+  return avgpool_backward(stream, b16_pool_blocks, dy, dx, rows, s);
 }

@@ -60,4 +60,14 @@ __device__ __forceinline__ T block_sum(T v, T* smem /* >= 16 entries */) {
   return r;
 }
 
+// ---- scalar bf16 <-> fp32 (bf16 travels as unsigned short) --------------------------------
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef float f32x2v __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ float bf2f(unsigned short v) { return __builtin_bit_cast(float, (unsigned)v << 16); }
+__device__ __forceinline__ unsigned short f2bf(float a) {        // round to nearest even (v_cvt_pk_bf16_f32)
+  f32x2v v = {a, 0.f};
+  return (unsigned short)(__builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2)) & 0xffffu);
+}
+
 }  // namespace cstp

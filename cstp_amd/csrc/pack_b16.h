@@ -9,13 +9,6 @@
 
 namespace cstp {
 
-typedef __bf16 pk_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float pk_f32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned short pack_f2bf(float a) {        // round to nearest even (v_cvt_pk_bf16_f32)
-  pk_f32x2 v = {a, 0.f};
-  return (unsigned short)(__builtin_bit_cast(unsigned, __builtin_convertvector(v, pk_bf16x2)) & 0xffffu);
-}
-
 __device__ __forceinline__ void pack_w_b16_body(const float* __restrict__ w, unsigned short* __restrict__ wp, int kout, int cin, int ntaps,
                                                 int Mp, int Kw, int dgrad, int ip, int blk, int nblk) {
   const size_t total = (size_t)Mp * Kw;
@@ -25,7 +18,7 @@ __device__ __forceinline__ void pack_w_b16_body(const float* __restrict__ w, uns
     const int tap = k / ip, c = k - tap * ip;
     float v = 0.f;
     if (m < mreal && tap < ntaps && c < inner) v = dgrad ? w[((size_t)c * cin + m) * ntaps + tap] : w[((size_t)m * cin + c) * ntaps + tap];
-    wp[i] = pack_f2bf(v);
+    wp[i] = f2bf(v);
   }
 }
 

@@ -1031,28 +1031,41 @@ def bn_relu_conv3d(x, gamma, beta, running_mean, running_var, w, stride=1, paddi
 
 
 # ----------------------------------------------------------------------------------------------
-# global average pool
+# pooling: global average pool and MaxPool3d, fp32 or bf16 storage
 # ----------------------------------------------------------------------------------------------
+def _pool_storage(dtype):
+    """(req, torch dtype, symbol prefix) of a pooling call: bfloat16 activations are the bf16-storage path, anything else must
+    pass _req as float32.  The prefix completes to cstp_avgpool_forward / _backward, cstp_maxpool3d_forward / _backward and
+    cstp_b16_avgpool_forward / _backward, cstp_b16_maxpool3d_forward / _backward."""
+    return (_req16, torch.bfloat16, "cstp_b16_") if dtype == torch.bfloat16 else (_req, torch.float32, "cstp_")
+
+
 class _AvgPool(torch.autograd.Function):
+    """T in, float32 out (the heads behind it are fp32); float32 dy, dx in the input's dtype."""
+
     @staticmethod
     def forward(ctx, x):
         lib = _lib.load()
-        x = _req(x, "avgpool input")
+        req, _, prefix = ctx.storage = _pool_storage(x.dtype)
+        x = req(x, "avgpool input")
         n, c = x.shape[0], x.shape[1]
         s = x.numel() // (n * c)
         y = torch.empty((n, c), dtype=torch.float32, device=x.device)
-        check(lib.cstp_avgpool_forward(_stream(), x.data_ptr(), y.data_ptr(), n * c, s), "cstp_avgpool_forward")
+        name = prefix + "avgpool_forward"
+        check(getattr(lib, name)(_stream(), x.data_ptr(), y.data_ptr(), n * c, s), name)
         ctx.shape = tuple(x.shape)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         lib = _lib.load()
+        _, dtype, prefix = ctx.storage
         dy = _req(dy, "avgpool grad_output")
-        dx = torch.empty(ctx.shape, dtype=torch.float32, device=dy.device)
+        dx = torch.empty(ctx.shape, dtype=dtype, device=dy.device)
         n, c = ctx.shape[0], ctx.shape[1]
         s = dx.numel() // (n * c)
-        check(lib.cstp_avgpool_backward(_stream(), dy.data_ptr(), dx.data_ptr(), n * c, s), "cstp_avgpool_backward")
+        name = prefix + "avgpool_backward"
+        check(getattr(lib, name)(_stream(), dy.data_ptr(), dx.data_ptr(), n * c, s), name)
         return dx
 
 
@@ -1060,7 +1073,8 @@ class _MaxPool3d(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, kernel, stride, padding):
         lib = _lib.load()
-        x = _req(x, "max_pool3d input")
+        req, dtype, prefix = ctx.storage = _pool_storage(x.dtype)
+        x = req(x, "max_pool3d input")
         if x.dim() != 5:
             raise _lib.CstpError("max_pool3d expects [N, C, D, H, W], got %s" % (tuple(x.shape),))
         n, c, d, h, w = x.shape
@@ -1068,10 +1082,10 @@ class _MaxPool3d(torch.autograd.Function):
         st = (ctypes.c_int32 * 3)(*stride)
         pd = (ctypes.c_int32 * 3)(*padding)
         osz = tuple((sz + 2 * padding[i] - kernel[i]) // stride[i] + 1 for i, sz in enumerate((d, h, w)))
-        y = torch.empty((n, c) + osz, dtype=torch.float32, device=x.device)
+        y = torch.empty((n, c) + osz, dtype=dtype, device=x.device)
         idx = torch.empty((n, c) + osz, dtype=torch.int32, device=x.device)
-        check(lib.cstp_maxpool3d_forward(_stream(), x.data_ptr(), y.data_ptr(), idx.data_ptr(), n * c, d, h, w, k, st, pd),
-              "cstp_maxpool3d_forward")
+        name = prefix + "maxpool3d_forward"
+        check(getattr(lib, name)(_stream(), x.data_ptr(), y.data_ptr(), idx.data_ptr(), n * c, d, h, w, k, st, pd), name)
         ctx.save_for_backward(idx)
         ctx.geom = (tuple(x.shape), tuple(kernel), tuple(stride), tuple(padding))
         return y
@@ -1081,26 +1095,24 @@ class _MaxPool3d(torch.autograd.Function):
         lib = _lib.load()
         (idx,) = ctx.saved_tensors
         shape, kernel, stride, padding = ctx.geom
-        dy = _req(dy, "max_pool3d grad_output")
-        dx = torch.empty(shape, dtype=torch.float32, device=dy.device)
+        req, dtype, prefix = ctx.storage
+        dy = req(dy, "max_pool3d grad_output")
+        dx = torch.empty(shape, dtype=dtype, device=dy.device)
         n, c, d, h, w = shape
-        check(lib.cstp_maxpool3d_backward(_stream(), dy.data_ptr(), idx.data_ptr(), dx.data_ptr(), n * c, d, h, w,
-                                          (ctypes.c_int32 * 3)(*kernel), (ctypes.c_int32 * 3)(*stride),
-                                          (ctypes.c_int32 * 3)(*padding)), "cstp_maxpool3d_backward")
+        name = prefix + "maxpool3d_backward"
+        check(getattr(lib, name)(_stream(), dy.data_ptr(), idx.data_ptr(), dx.data_ptr(), n * c, d, h, w,
+                                 (ctypes.c_int32 * 3)(*kernel), (ctypes.c_int32 * 3)(*stride), (ctypes.c_int32 * 3)(*padding)),
+              name)
         return dx, None, None, None
 
 
 def max_pool3d(x, kernel_size=3, stride=2, padding=1):
-    """nn.MaxPool3d(kernel_size, stride, padding) (models/BE/r3d_byol.py:158)."""
-    if x.dtype == torch.bfloat16:
-        return _MaxPool3dB16.apply(x, _triple(kernel_size), _triple(stride), _triple(padding))
+    """nn.MaxPool3d(kernel_size, stride, padding) (models/BE/r3d_byol.py:158); float32 or bfloat16, y and dx in x's dtype."""
     return _MaxPool3d.apply(x, _triple(kernel_size), _triple(stride), _triple(padding))
 
 
 def global_avg_pool(x):
     """AdaptiveAvgPool3d(1) + view(-1, C).  bfloat16 in -> float32 out (the heads behind it are fp32)."""
-    if x.dtype == torch.bfloat16:
-        return _AvgPoolB16.apply(x)
     return _AvgPool.apply(x)
 
 
@@ -1548,61 +1560,6 @@ class _BNActB16(torch.autograd.Function):
         if dres is not None and ctx.grad_join is not None:       # the residual tensor's other consumer adds its gradient to this
             dres = ctx.grad_join.contribute(lambda: dres, lambda buf: buf.add_(dres))
         return dx, dgamma, dbeta, dres, None, None, None, None, None, None, None
-
-
-class _MaxPool3dB16(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, kernel, stride, padding):
-        lib = _lib.load()
-        x = _req16(x, "max_pool3d input")
-        if x.dim() != 5:
-            raise _lib.CstpError("max_pool3d expects [N, C, D, H, W], got %s" % (tuple(x.shape),))
-        n, c, d, h, w = x.shape
-        osz = tuple((sz + 2 * padding[i] - kernel[i]) // stride[i] + 1 for i, sz in enumerate((d, h, w)))
-        y = torch.empty((n, c) + osz, dtype=torch.bfloat16, device=x.device)
-        idx = torch.empty((n, c) + osz, dtype=torch.int32, device=x.device)
-        check(lib.cstp_b16_maxpool3d_forward(_stream(), x.data_ptr(), y.data_ptr(), idx.data_ptr(), n * c, d, h, w,
-                                             (ctypes.c_int32 * 3)(*kernel), (ctypes.c_int32 * 3)(*stride),
-                                             (ctypes.c_int32 * 3)(*padding)), "cstp_b16_maxpool3d_forward")
-        ctx.save_for_backward(idx)
-        ctx.geom = (tuple(x.shape), tuple(kernel), tuple(stride), tuple(padding))
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        lib = _lib.load()
-        (idx,) = ctx.saved_tensors
-        shape, kernel, stride, padding = ctx.geom
-        dy = _req16(dy, "max_pool3d grad_output")
-        dx = torch.empty(shape, dtype=torch.bfloat16, device=dy.device)
-        n, c, d, h, w = shape
-        check(lib.cstp_b16_maxpool3d_backward(_stream(), dy.data_ptr(), idx.data_ptr(), dx.data_ptr(), n * c, d, h, w,
-                                              (ctypes.c_int32 * 3)(*kernel), (ctypes.c_int32 * 3)(*stride),
-                                              (ctypes.c_int32 * 3)(*padding)), "cstp_b16_maxpool3d_backward")
-        return dx, None, None, None
-
-
-class _AvgPoolB16(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x):
-        lib = _lib.load()
-        x = _req16(x, "avgpool input")
-        n, c = x.shape[0], x.shape[1]
-        s = x.numel() // (n * c)
-        y = torch.empty((n, c), dtype=torch.float32, device=x.device)
-        check(lib.cstp_b16_avgpool_forward(_stream(), x.data_ptr(), y.data_ptr(), n * c, s), "cstp_b16_avgpool_forward")
-        ctx.shape = tuple(x.shape)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        lib = _lib.load()
-        dy = _req(dy, "avgpool grad_output")
-        dx = torch.empty(ctx.shape, dtype=torch.bfloat16, device=dy.device)
-        n, c = ctx.shape[0], ctx.shape[1]
-        check(lib.cstp_b16_avgpool_backward(_stream(), dy.data_ptr(), dx.data_ptr(), n * c, dx.numel() // (n * c)),
-              "cstp_b16_avgpool_backward")
-        return dx
 
 
 # ----------------------------------------------------------------------------------------------
