@@ -209,6 +209,10 @@ SIGNATURES = {
     "cstp_ntxq_forward": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_float, _P, c_size_t]),
     "cstp_ntxq_backward": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_float, _P, c_size_t]),
     "cstp_ntxq_push": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, c_int32]),
+    # spherical k-means on cached features: assignment and centroid update of all restarts (csrc/kmeans.h)
+    "cstp_kmeans_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "cstp_kmeans_assign": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, c_size_t]),
+    "cstp_kmeans_update": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P]),
 }
 
 _lib = None

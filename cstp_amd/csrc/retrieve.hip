@@ -363,3 +363,4 @@ extern "C" int cstp_knn_vote(void* stream, const float* val, const int32_t* idx,
 
 #include "probe.h"  // the linear probe on cached features: cstp_probe_step, cstp_probe_predict
 #include "ntxq.h"   // NT-Xent with a queue of negatives: cstp_ntxq_forward, cstp_ntxq_backward, cstp_ntxq_push
+#include "kmeans.h"  // spherical k-means on cached features: cstp_kmeans_assign, cstp_kmeans_update

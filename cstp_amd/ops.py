@@ -2210,6 +2210,102 @@ def probe_predict(x, w, b, mean=None, inv_std=None, n_top=5):
     return pred, score
 
 
+KMEANS_MAX_ROWS, KMEANS_MAX_DIM, KMEANS_MAX_CLUSTERS, KMEANS_MAX_RESTARTS = 1 << 24, 4096, 4096, 32
+
+
+def _kmeans_operands(op, x, cent):
+    """The shared checks of kmeans_assign / kmeans_update on (x [n, d], cent [r, c, d]) -> (n, d, c, r)."""
+    if x.dim() != 2:
+        raise _lib.CstpError("%s: x must be [rows, features], got %s" % (op, tuple(x.shape)))
+    if cent.dim() != 3 or cent.shape[2] != x.shape[1]:
+        raise _lib.CstpError("%s: cent must be [restarts, clusters, %d], got %s" % (op, x.shape[1], tuple(cent.shape)))
+    for t, name in ((x, "x"), (cent, "cent")):
+        if t.dtype != torch.float32:
+            raise _lib.CstpError("%s: %s must be float32, got %s" % (op, name, t.dtype))
+    n, d = x.shape
+    r, c = cent.shape[0], cent.shape[1]
+    if n < 1 or d < 1 or c < 1 or r < 1:
+        raise _lib.CstpError("%s: empty operand, x is %s and cent %s" % (op, tuple(x.shape), tuple(cent.shape)))
+    if n > KMEANS_MAX_ROWS or d > KMEANS_MAX_DIM or c > KMEANS_MAX_CLUSTERS or r > KMEANS_MAX_RESTARTS:
+        raise _lib.CstpError("%s: at most %d rows, %d features, %d clusters and %d restarts are served, got x %s and cent %s"
+                             % (op, KMEANS_MAX_ROWS, KMEANS_MAX_DIM, KMEANS_MAX_CLUSTERS, KMEANS_MAX_RESTARTS, tuple(x.shape),
+                                tuple(cent.shape)))
+    if c > n:
+        raise _lib.CstpError("%s: %d clusters for %d rows: the number of clusters must not exceed the rows" % (op, c, n))
+    return n, d, c, r
+
+
+def _kmeans_assignment(op, t, name, r, n):
+    if t.dim() != 2 or tuple(t.shape) != (r, n):
+        raise _lib.CstpError("%s: %s must be [%d, %d] (restarts, rows), got %s" % (op, name, r, n, tuple(t.shape)))
+    if t.dtype != torch.int32:
+        raise _lib.CstpError("%s: %s must be int32, got %s" % (op, name, t.dtype))
+
+
+def _kmeans_out(op, out, specs, device):
+    """``out``: preallocated results, checked against (name, shape, dtype) -- or None: new tensors."""
+    if out is None:
+        return tuple(torch.empty(shape, dtype=dtype, device=device) for _, shape, dtype in specs)
+    if len(out) != len(specs):
+        raise _lib.CstpError("%s: out must be (%s)" % (op, ", ".join(name for name, _, _ in specs)))
+    for t, (name, shape, dtype) in zip(out, specs):
+        if tuple(t.shape) != tuple(shape) or t.dtype != dtype:
+            raise _lib.CstpError("%s: out %s must be %s of shape %s, got %s %s" % (op, name, dtype, tuple(shape), t.dtype, tuple(t.shape)))
+        if t.device != device or not t.is_contiguous():
+            raise _lib.CstpError("%s: out %s must be contiguous and on %s" % (op, name, device))
+    return tuple(out)
+
+
+def kmeans_assign(x, cent, prev=None, out=None):
+    """The assignment step of spherical k-means for all restarts in one call (include/cstp_hip.h: cstp_kmeans_assign): x [n, d]
+    fp32 rows, cent [r, c, d] fp32 centroids (both L2-normalised by the caller), prev [r, n] int32 or None ->
+    (assign [r, n] int32, best [r, n] fp32, moved [r] int32, score [r] fp64): every row's most similar centroid of every restart
+    -- the bits of sim_topk(x, cent[s], 1), the lowest id among bit-equal similarities --, the number of rows whose assignment
+    differs from prev (n without prev) and the fp64 sum of best in a fixed order.  No [n, c] table, no atomics, nothing read back;
+    the scratch is private and exact.  ``out`` = (assign, best, moved, score) preallocated: then only the scratch is allocated.
+    No autograd."""
+    op = "kmeans_assign"
+    n, d, c, r = _kmeans_operands(op, x, cent)
+    if prev is not None:
+        _kmeans_assignment(op, prev, "prev", r, n)
+    named = [(x, "x"), (cent, "cent"), (prev, "prev")]
+    _probe_devices(op, named)
+    x, cent = x.detach(), cent.detach()
+    for t, name in named:
+        if t is not None:
+            _probe_c(op, t, name)
+    lib = _lib.load()
+    dev = x.device
+    ws = torch.empty(lib.cstp_kmeans_workspace_bytes(n, d, c, r), dtype=torch.uint8, device=dev)    # private and exact
+    assign, best, moved, score = _kmeans_out(op, out, (("assign", (r, n), torch.int32), ("best", (r, n), torch.float32),
+                                                       ("moved", (r,), torch.int32), ("score", (r,), torch.float64)), dev)
+    check(lib.cstp_kmeans_assign(_stream(), x.data_ptr(), cent.data_ptr(), _ptr(prev), n, d, c, r, assign.data_ptr(), best.data_ptr(),
+                                 moved.data_ptr(), score.data_ptr(), ws.data_ptr(), ws.numel()), "cstp_kmeans_assign")
+    return assign, best, moved, score
+
+
+def kmeans_update(x, assign, cent, out=None):
+    """The centroid step of spherical k-means for all restarts in one call (include/cstp_hip.h: cstp_kmeans_update): x [n, d] fp32,
+    assign [r, n] int32, cent [r, c, d] fp32 (the centroids the assignment was made with) -> (cent_new [r, c, d] fp32,
+    counts [r, c] int32): the L2-normalised fp32 sum of every cluster's rows, added in ascending row order, and the clusters'
+    sizes.  A cluster without rows (or whose sum has no length) keeps its row of ``cent``; an assign value outside 0..c-1 belongs
+    to no cluster.  cent_new is a new tensor, or ``out`` = (cent_new, counts) preallocated; it may not overlap ``cent``.  One
+    launch, no atomics, equal bits on equal inputs.  No autograd."""
+    op = "kmeans_update"
+    n, d, c, r = _kmeans_operands(op, x, cent)
+    _kmeans_assignment(op, assign, "assign", r, n)
+    named = [(x, "x"), (cent, "cent"), (assign, "assign")]
+    _probe_devices(op, named)
+    x, cent = x.detach(), cent.detach()
+    for t, name in named:
+        _probe_c(op, t, name)
+    lib = _lib.load()
+    cent_new, counts = _kmeans_out(op, out, (("cent_new", (r, c, d), torch.float32), ("counts", (r, c), torch.int32)), x.device)
+    check(lib.cstp_kmeans_update(_stream(), x.data_ptr(), assign.data_ptr(), cent.data_ptr(), n, d, c, r, cent_new.data_ptr(),
+                                 counts.data_ptr()), "cstp_kmeans_update")
+    return cent_new, counts
+
+
 # ----------------------------------------------------------------------------------------------
 # flat-arena utilities (no autograd)
 # ----------------------------------------------------------------------------------------------

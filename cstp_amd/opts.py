@@ -42,6 +42,11 @@ Additions (all optional, defaults reproduce the reference):
   --probe_wd        its weight decay on the weight matrix, >= 0 (default 0; decoupled with adam, coupled with sgd)
   --probe_optimizer adam | sgd (momentum 0.9) (default adam); the number of classes is --n_finetune_classes; the defaults are
                     conventional choices, not tuned on real data (every other driver ignores all five)
+  --cluster_k       k-means clustering evaluation (cluster.py): the number of clusters, >= 0; 0 = --n_finetune_classes (default 0)
+  --cluster_iters   its Lloyd iterations per restart, exactly that many (no early stop: nothing is read back), >= 1 (default 50)
+  --cluster_restarts  its k-means++ restarts, run side by side in one launch, 1..32; the best final score wins (default 10); the
+                    seed is --manual_seed; the defaults are conventional choices, not tuned on real data (every other driver
+                    ignores all three)
 torchrun passes LOCAL_RANK through the environment instead of --local_rank; both are honoured.
 """
 from __future__ import annotations
@@ -193,6 +198,30 @@ def _probe_wd(text):
     return v
 
 
+CLUSTER_MAX_RESTARTS = 32    # ops.KMEANS_MAX_RESTARTS: the restart is a grid dimension of the kernels
+
+
+def _cluster_k(text):
+    k = int(text)
+    if k < 0:
+        raise argparse.ArgumentTypeError("--cluster_k must be >= 0 (0 = --n_finetune_classes), got %d" % k)
+    return k
+
+
+def _cluster_iters(text):
+    v = int(text)
+    if v < 1:
+        raise argparse.ArgumentTypeError("--cluster_iters must be >= 1, got %d" % v)
+    return v
+
+
+def _cluster_restarts(text):
+    v = int(text)
+    if not 1 <= v <= CLUSTER_MAX_RESTARTS:
+        raise argparse.ArgumentTypeError("--cluster_restarts takes values in 1..%d, got %d" % (CLUSTER_MAX_RESTARTS, v))
+    return v
+
+
 def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(description="CSTP pre-training on MI355X")
     for name, default, typ, text in _FLAGS:
@@ -214,6 +243,13 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--probe_lr", default=1e-3, type=_probe_lr, help="linear_probe.py: peak learning rate (cosine to 0), > 0")
     parser.add_argument("--probe_wd", default=0.0, type=_probe_wd, help="linear_probe.py: weight decay on the weight matrix, >= 0")
     parser.add_argument("--probe_optimizer", default="adam", choices=("adam", "sgd"), help="linear_probe.py: the update rule")
+    parser.add_argument("--cluster_k", default=0, type=_cluster_k,
+                        help="cluster.py: number of k-means clusters, 0 = --n_finetune_classes")
+    parser.add_argument("--cluster_iters", default=50, type=_cluster_iters,
+                        help="cluster.py: Lloyd iterations per restart, >= 1 (a conventional choice, not tuned on real data)")
+    parser.add_argument("--cluster_restarts", default=10, type=_cluster_restarts,
+                        help="cluster.py: k-means++ restarts, 1..%d, the best final score wins (a conventional choice, not tuned "
+                             "on real data)" % CLUSTER_MAX_RESTARTS)
     return parser
 
 

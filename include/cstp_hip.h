@@ -772,6 +772,45 @@ int cstp_ntxq_backward(void* stream, const float* reps, const float* queue, cons
                        int32_t f, int32_t cap, int32_t n_valid, float temperature, void* ws, size_t ws_bytes);
 int cstp_ntxq_push(void* stream, const float* reps, float* queue, int32_t R, int32_t f, int32_t cap, int32_t ptr);
 
+/* ---- spherical k-means on cached features: Lloyd's iteration for R restarts at once (csrc/kmeans.h, included from
+ * csrc/retrieve.hip) ------------------------------------------------------------------------------------
+ * x [n][d] fp32 rows and cent [r][c][d] fp32 centroids of r independent restarts, both L2-normalised by the caller, FINITE.
+ * A row belongs to the centroid with the largest dot product.
+ *
+ * cstp_kmeans_assign: for every restart s and row i
+ *   best[s][i]   = max_j sim(i, j),  sim(i, j) = sum_f x[i][f] * cent[s][j][f]: cstp_simtopk's fmaf chain over ascending features on
+ *                  v_mfma_f32_32x32x2_f32, so (best, assign) holds the bits of cstp_simtopk(x, cent[s], k = 1)
+ *   assign[s][i] = the j that attains it, the LOWEST j where several similarities are bit-equal (int32)
+ *   moved[s]     = the number of rows with assign[s][i] != prev[s][i] (int32); n when prev is NULL
+ *   score[s]     = sum_i best[s][i] in fp64: the 64 rows of a tile through one shuffle tree, the tiles in ascending order strided
+ *                  over 256 threads, those through one tree -- a fixed order that depends on n alone
+ * One block owns 64 rows and one restart and streams that restart's centroids in tiles of 128 with a running best in registers:
+ * no [n][c] table, no insertion list.  Two launches (the walk; the fold of the per-tile partials), no atomics, nothing read
+ * back.  Restart s of a batch gets the bits it gets alone.  prev may not overlap assign.  Workspace: r * ceil(n / 64) doubles
+ * and as many int32, each plane rounded up to 16 bytes = cstp_kmeans_workspace_bytes(n, d, c, r), a pure host function (0 on
+ * bad arguments); ws must be 16-byte aligned.
+ *
+ * cstp_kmeans_update: cent_out[s][j] = sum / |sum| of the rows with assign[s][i] == j, counts[s][j] = their number (int32).
+ *   sum[f]  = (((0 + x[i_1][f]) + x[i_2][f]) + ...) in fp32 over those rows in ASCENDING ROW ORDER: one chain per (cluster,
+ *             feature); the order depends on (n, assign) alone -- never on the grid, the block count or r
+ *   |sum|^2 = thread t of 256 folds sum[f]^2 by fmaf over f = t, t + 256, ... ascending; the 256 partials go through one fixed tree
+ *   out[f]  = sum[f] * (1.0f / sqrtf(|sum|^2)), division and square root correctly rounded
+ * A cluster with counts == 0, or whose |sum|^2 is not > 0, keeps cent_in[s][j] bit for bit.  An assign value outside 0..c-1
+ * belongs to no cluster: it is compared, never used to form an address.  One launch, one block per (cluster, restart), no
+ * workspace, no atomics.  cent_out may not overlap cent_in.  Once an assign call reports moved == 0, further assign / update
+ * rounds reproduce cent and assign bit for bit: Lloyd's iteration is at a fixed point.
+ *
+ * Limits, refused with a message before any HIP call: 1 <= n <= 2^24, 1 <= d <= 4096, 1 <= c <= 4096, c <= n, 1 <= r <= 32; a
+ * NULL among the required pointers (all but prev); overlapping cent_in / cent_out or prev / assign; ws unaligned or too small.
+ * d need not be a multiple of 4 and no pointer need be 16-byte aligned (then operands are staged by scalar loads).
+ * The limits are what the indexing supports, not a promise of speed: every update block reads all of assign[s], c * n * 4 bytes
+ * per restart, which suits n ~ 10^4 - 10^5 and c ~ 10^2 (105 MB at n = 65 536, c = 400) and takes many seconds at the limits. */
+size_t cstp_kmeans_workspace_bytes(int32_t n, int32_t d, int32_t c, int32_t r);
+int cstp_kmeans_assign(void* stream, const float* x, const float* cent, const int32_t* prev, int32_t n, int32_t d, int32_t c,
+                       int32_t r, int32_t* assign, float* best, int32_t* moved, double* score, void* ws, size_t ws_bytes);
+int cstp_kmeans_update(void* stream, const float* x, const int32_t* assign, const float* cent_in, int32_t n, int32_t d, int32_t c,
+                       int32_t r, float* cent_out, int32_t* counts);
+
 #ifdef __cplusplus
 }
 #endif
