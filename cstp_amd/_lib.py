@@ -142,6 +142,10 @@ SIGNATURES = {
     "cstp_clip_batch_forward": (c_int32, [_P, _P, _P, c_int32, c_int32, c_int32, _P, c_int32, _P, c_int64, _P, c_int32, _P,
                                           c_int32]),
     "cstp_clip_mix": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32]),
+    # RandAugment layers and the erasing finish of a batch of 8-bit clips (csrc/randaug.h)
+    "cstp_randaug_entry_bytes": (c_size_t, []),
+    "cstp_randaug_layer": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int32, c_int32, _P, _P]),
+    "cstp_randaug_finish": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32]),
     "cstp_ema_update": (c_int32, [_P, _P, _P, c_size_t, c_double]),
     "cstp_sumsq": (c_int32, [_P, _P, c_size_t, _P, _P, c_size_t]),
     "cstp_clip_coef": (c_int32, [_P, _P, c_float, _P, _P]),

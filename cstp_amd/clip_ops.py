@@ -23,7 +23,7 @@ from typing import List
 import numpy as np
 import torch
 
-from . import _lib, sampler
+from . import _lib, randaug, sampler
 from ._lib import check
 
 PRECISION_BITS = 32 - 8 - 2        # Pillow: libImaging/Resample.c
@@ -349,6 +349,8 @@ def assemble_batch(videos, plans, size: int, out: torch.Tensor = None) -> torch.
             raise ValueError("assemble_batch serves crop / scale / window / jitter plans; rotated and base_transform clips go "
                              "through assemble_clip")
     jittered = [i for i, p in enumerate(plans) if getattr(p, "jitter", None)]
+    if any(getattr(p, "randaug", None) or getattr(p, "erase", None) is not None for p in plans):
+        return _assemble_augmented(videos, plans, size, out, jittered)
     out, u8 = _batch_forward(videos, plans, size, out, jittered)
     lib, st = _lib.load(), torch.cuda.current_stream().cuda_stream
     t = len(plans[0].frames)
@@ -361,11 +363,84 @@ def assemble_batch(videos, plans, size: int, out: torch.Tensor = None) -> torch.
     return out
 
 
+def _assemble_augmented(videos, plans, size: int, out, jittered):
+    """assemble_batch when some plan carries ``randaug`` or ``erase``: EVERY clip leaves the resize as 8-bit frames in slot i of one
+    buffer, jittered clips take today's per-clip colour calls on their slot first (the jitter precedes RandAugment in the
+    transform), then ``augment_batch`` serves the whole buffer.  The operation tables ride in the descriptor upload."""
+    flips = [bool(getattr(p, "flip", False)) for p in plans]
+    packed = randaug.tables(plans, flips, size)
+    out, u8, tables = _batch_forward_with(videos, plans, size, out, list(range(len(plans))), packed)
+    for i in jittered:
+        clip = u8[i]
+        for op, factor in plans[i].jitter:
+            clip = clip_colour(clip, op, factor)
+        u8[i].copy_(clip)
+    augment_batch(u8, plans, out, flips, tables=tables)
+    return out
+
+
+def augment_batch(u8: torch.Tensor, plans, out: torch.Tensor, flips, tables=None):
+    """RandAugment layers and the erasing finish over a batch of 8-bit clips: u8 [n][t][s][s][3] (uint8, one HIP device), clip i
+    under ``plans[i].randaug`` ([(operation, value)], cstp_amd.randaug) -> [flip if flips[i]] -> tensor -> ``plans[i].erase``
+    -> out[i] (fp32 [n][3][t][s][s]).  Per layer one cstp_randaug_layer (a statistics launch only when some clip's operation is
+    AutoContrast, Equalize or Contrast, and the apply launch), then one cstp_randaug_finish: at most 2 L + 1 launches for L layers,
+    whatever n is.  The twin buffer, the look-up tables and the means are allocated once per call; ``u8`` is the other half of the
+    ping-pong and is overwritten from the second layer on.  ``tables``: (pinned host bytes, their device copy) of
+    ``randaug.tables(plans, flips, s)`` when the caller has uploaded them already.
+    -> (out, the 8-bit clips after the last layer: ``u8`` or its twin)."""
+    lib = _lib.load()
+    plans = list(plans)
+    if not u8.is_cuda or u8.dtype != torch.uint8 or u8.dim() != 5 or u8.shape[4] != 3 or u8.shape[2] != u8.shape[3] \
+            or not u8.is_contiguous():
+        raise _lib.CstpError("expected contiguous uint8 [N, T, S, S, 3] clips on a HIP device (cstp_amd has no CPU path)")
+    n, t, s = int(u8.shape[0]), int(u8.shape[1]), int(u8.shape[2])
+    if len(plans) != n or len(flips) != n:
+        raise ValueError("%d plans and %d flips for %d clips" % (len(plans), len(flips), n))
+    if out.shape != (n, 3, t, s, s) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != u8.device:
+        raise ValueError("out must be a contiguous fp32 [%d, 3, %d, %d, %d] tensor on %s" % (n, t, s, s, u8.device))
+    if lib.cstp_randaug_entry_bytes() != randaug.ENTRY.itemsize or randaug.FINISH_ENTRY.itemsize != randaug.ENTRY.itemsize:
+        raise _lib.CstpError("cstp_randaug_entry is %d bytes in the library, %d here"
+                             % (lib.cstp_randaug_entry_bytes(), randaug.ENTRY.itemsize))
+    layers = randaug.n_layers(plans)
+    if tables is None:
+        packed = randaug.tables(plans, flips, s)
+        host = torch.empty(packed.size, dtype=torch.uint8, pin_memory=True)
+        host.numpy()[:] = packed
+        dev = torch.empty(packed.size, dtype=torch.uint8, device=u8.device)
+        dev.copy_(host, non_blocking=True)
+    else:
+        host, dev = tables
+    step = n * randaug.ENTRY.itemsize
+    if host.numel() != (layers + 1) * step or dev.numel() != host.numel():
+        raise ValueError("operation tables of %d bytes for %d layers of %d clips" % (host.numel(), layers, n))
+    ops = host.numpy()[:layers * step].view(randaug.ENTRY)["op"]
+    stats = bool(np.isin(ops, (randaug.RA_AUTOCONTRAST, randaug.RA_EQUALIZE, randaug.RA_CONTRAST)).any())
+    lut = torch.empty((n, t, 3, 256), dtype=torch.uint8, device=u8.device) if stats else None
+    mean = torch.empty((n, t), dtype=torch.int32, device=u8.device) if stats else None
+    st = torch.cuda.current_stream().cuda_stream
+    src, dst = u8, (torch.empty_like(u8) if layers else None)
+    for l in range(layers):
+        check(lib.cstp_randaug_layer(st, src.data_ptr(), dst.data_ptr(), dev.data_ptr() + l * step, host.data_ptr() + l * step, n, t, s,
+                                     None if lut is None else lut.data_ptr(), None if mean is None else mean.data_ptr()),
+              "cstp_randaug_layer")
+        src, dst = dst, src
+    check(lib.cstp_randaug_finish(st, src.data_ptr(), out.data_ptr(), dev.data_ptr() + layers * step, host.data_ptr() + layers * step,
+                                  n, t, s, n), "cstp_randaug_finish")
+    return out, src
+
+
 def _batch_forward(videos, plans, size: int, out, eight_bit):
+    """``_batch_forward_with`` without a payload -> (out, u8)."""
+    return _batch_forward_with(videos, plans, size, out, eight_bit, None)[:2]
+
+
+def _batch_forward_with(videos, plans, size: int, out, eight_bit, extra):
     """The descriptor table, its one pinned upload and the two launches of cstp_clip_batch_forward for ``plans`` (any mix of
     FtClipPlan / ClipPlan: ``rotate`` is honoured here).  The clips listed in ``eight_bit`` stop after the resize as uint8
     [t][size][size][3] (no flip, no normalisation) for the caller's 8-bit operations; every other clip i is finished into
-    out[i].  -> (out fp32 [n][3][t][size][size], u8 [len(eight_bit)][t][size][size][3] or None)."""
+    out[i].  ``extra`` (uint8 numpy bytes) rides behind the table in the same upload, on a 16-byte boundary.
+    -> (out fp32 [n][3][t][size][size], u8 [len(eight_bit)][t][size][size][3] or None,
+        (pinned host view, device view) of ``extra`` or None)."""
     lib = _lib.load()
     n = len(plans)
     if torch.is_tensor(videos):
@@ -379,10 +454,15 @@ def _batch_forward(videos, plans, size: int, out, eight_bit):
     t = len(plans[0].frames)
     slot8 = {i: j for j, i in enumerate(eight_bit)}
     nbytes = n * _BATCH_DESC.itemsize + 4 * n * t
+    extra_off = (nbytes + 15) // 16 * 16
+    if extra is not None:
+        nbytes = extra_off + extra.size
     host = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
     view = host.numpy()
     desc = view[:n * _BATCH_DESC.itemsize].view(_BATCH_DESC)
-    idx = view[n * _BATCH_DESC.itemsize:].view(np.int32)
+    idx = view[n * _BATCH_DESC.itemsize:n * _BATCH_DESC.itemsize + 4 * n * t].view(np.int32)
+    if extra is not None:
+        view[extra_off:] = extra
     tmp_pixels = 0
     for i, (v, p) in enumerate(zip(videos, plans)):
         if not v.is_cuda or v.dtype != torch.uint8 or v.dim() != 4 or v.shape[3] != 3 or not v.is_contiguous() or v.device != dev:
@@ -421,7 +501,7 @@ def _batch_forward(videos, plans, size: int, out, eight_bit):
                                       table.data_ptr() + n * _BATCH_DESC.itemsize, n * t, tmp.data_ptr(), tmp_pixels,
                                       out.data_ptr(), n, None if u8 is None else u8.data_ptr(), len(slot8)),
           "cstp_clip_batch_forward")
-    return out, u8
+    return out, u8, (None if extra is None else (host[extra_off:], table[extra_off:]))
 
 
 def assemble_pairs(videos, pair_plans, size: int, out: torch.Tensor = None):
@@ -452,6 +532,19 @@ def assemble_pairs(videos, pair_plans, size: int, out: torch.Tensor = None):
     return flat[:b], flat[b:]
 
 
+def augment_settings(randaug_nmstd, random_erase: float, data_type: str, mode: str):
+    """The ``randaug.Settings`` of a labelled data set's ``randaug=(n, m, mstd)`` (or None) and ``random_erase=P`` arguments, None
+    when both are off.  Only training clips under 'img' are augmented: anything else is refused."""
+    n, m, mstd = (0, 9.0, 0.0) if randaug_nmstd is None else randaug_nmstd
+    settings = randaug.Settings(n, float(m), float(mstd), float(random_erase))
+    if not settings.on:
+        return None
+    if data_type != "train" or mode != "img":
+        raise ValueError("randaug / random_erase augment training clips under 'img'; data_type %r with mode %r is never augmented"
+                         % (data_type, mode))
+    return settings
+
+
 def _labelled_video(label: int, n_classes: int, frames: int, height: int, width: int, gen, device) -> torch.Tensor:
     """uint8 [F][H][W][3]: a moving grating whose orientation, frequency, drift and colour phase are functions of the label,
     plus uniform noise -- separable by a classifier, and smooth enough that a resize is not all aliasing."""
@@ -472,15 +565,19 @@ class GpuLabelledVideos:
     class-dependent patterns, 240 x 320 by default so ClipScale really resizes) live in HBM, with mixed lengths -- the first is
     shorter than clip_range + 1 and takes the wrap-around branch, the second is exactly clip_range + 1.  'train' / 'val' items
     are one clip under ``mode`` ('img' / 'img_val'); a 'test' item is every clip of a video under 'img_test'.  Each sample's RNG
-    is seeded from (seed, epoch, index), so the augmentation of a video changes from epoch to epoch.  Selected by the fine-tune
-    and test drivers with ``--dataset synthetic_video``."""
+    is seeded from (seed, epoch, index), so the augmentation of a video changes from epoch to epoch.  ``randaug=(n, m, mstd)`` and
+    ``random_erase=P`` add RandAugment and random erasing to 'train' clips (cstp_amd.randaug: drawn from a second generator
+    seeded from the same three, so the plan's other fields do not move).  Selected by the fine-tune and test drivers with
+    ``--dataset synthetic_video``."""
 
     _SALT = {"train": 11, "val": 23, "test": 37}
+    augment = None                     # randaug.Settings of the ``randaug`` / ``random_erase`` arguments; None = off
 
     def __init__(self, device, data_type="train", mode="img", n_videos=8, n_classes=101, height=240, width=320, sample_duration=16,
-                 sample_size=112, pb_rate=4, length=None, seed=1, lengths=None):
+                 sample_size=112, pb_rate=4, length=None, seed=1, lengths=None, randaug=None, random_erase=0.0):
         if data_type not in self._SALT:
             raise ValueError("data_type %r" % (data_type,))
+        self.augment = augment_settings(randaug, random_erase, data_type, mode)
         sampler._check_ft_mode(mode)
         if (data_type == "test") != (mode == "img_test"):
             raise ValueError("data_type %r with transform mode %r: the video test takes 'img_test', train / val take 'img' / "
@@ -509,8 +606,11 @@ class GpuLabelledVideos:
         f, h, w, _ = self.videos[v].shape
         if self.data_type == "test":
             return v, sampler.plan_test_video(f, w, h, self.t, self.size, self.pb_rate, self.mode)
-        rng = random.Random(((self.seed * 1000003 + epoch) * 1000003 + index) * 101 + self._SALT[self.data_type])
-        return v, sampler.sample_ft_clip(f, w, h, self.t, self.size, self.pb_rate, self.mode, rng)
+        s = ((self.seed * 1000003 + epoch) * 1000003 + index) * 101 + self._SALT[self.data_type]
+        plan = sampler.sample_ft_clip(f, w, h, self.t, self.size, self.pb_rate, self.mode, random.Random(s))
+        if self.augment is not None:      # a generator of its own: the draws above keep their values
+            plan.randaug, plan.erase = randaug.draw(self.augment, self.size, randaug.clip_rng(s))
+        return v, plan
 
     def _labels(self, vs):
         return torch.tensor([self.labels[v] for v in vs], dtype=torch.int64).pin_memory().to(self.device, non_blocking=True)

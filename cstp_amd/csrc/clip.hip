@@ -13,7 +13,8 @@
 // The fine-tune / validation / video-test clips (datasets.py:952-1097 UcfFineTune, preprocess_data.py:1131-1149) come a BATCH at a
 // time through cstp_clip_batch_forward at the end of this file: one descriptor table, two launches for any number of clips.
 // A batch of pre-training pairs takes the same road, with a rotation code per clip (clip_ops.assemble_pairs).
-// Last in the file: cstp_clip_mix, mixup / CutMix of an assembled fp32 batch for fine-tuning (one launch, one table entry per sample).
+// Then cstp_clip_mix, mixup / CutMix of an assembled fp32 batch for fine-tuning (one launch, one table entry per sample), and last
+// randaug.h: RandAugment and random erasing on a batch of 8-bit clips, one operation table per layer.
 #include "common.h"
 
 namespace cstp {
@@ -615,3 +616,5 @@ extern "C" int cstp_clip_mix(void* stream, const float* x, float* y, const cstp_
   CSTP_LAUNCH_CHECK();
   return 0;
 }
+
+#include "randaug.h"   // RandAugment layers and the erasing finish of a batch of 8-bit clips: cstp_randaug_layer, cstp_randaug_finish

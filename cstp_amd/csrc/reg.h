@@ -15,38 +15,14 @@
 // The backward writes dz = scale[b] * g and dres = g (g = dy where y > 0, else 0) in one launch; either may be absent.
 #pragma once
 #include "common.h"
+#include "philox.h"
 
 namespace cstp {
 
 constexpr int REG_THREADS = 256;
 constexpr int REG_MAX_BLOCKS = 4096;      // memory-bound: a few blocks per CU, the rest by striding
 
-struct Philox4 { uint32_t v[4]; };
-
-__host__ __device__ __forceinline__ void philox_mulhilo(uint32_t a, uint32_t b, uint32_t& hi, uint32_t& lo) {
-  const uint64_t p = (uint64_t)a * (uint64_t)b;
-  hi = (uint32_t)(p >> 32);
-  lo = (uint32_t)p;
-}
-
-// Philox4x32 with 10 rounds (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11)
-__host__ __device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    uint32_t hi0, lo0, hi1, lo1;
-    philox_mulhilo(0xD2511F53u, c0, hi0, lo0);
-    philox_mulhilo(0xCD9E8D57u, c2, hi1, lo1);
-    c0 = hi1 ^ c1 ^ k0;
-    c1 = lo1;
-    c2 = hi0 ^ c3 ^ k1;
-    c3 = lo0;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  Philox4 o;
-  o.v[0] = c0; o.v[1] = c1; o.v[2] = c2; o.v[3] = c3;
-  return o;
-}
+// (Philox4, philox4x32_10: philox.h, shared with the erased box of randaug.h)
 
 // u = (w >> 8) * 2^-24 is exact in fp32; kept iff u >= p
 __device__ __forceinline__ float dropout_one(float x, uint32_t w, float p, float inv_keep) {

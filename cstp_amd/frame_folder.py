@@ -32,7 +32,8 @@ import torch
 from PIL import Image
 
 from . import sampler
-from .clip_ops import GpuClipLoader, GpuLabelledLoader, assemble_batch, assemble_pairs
+from . import randaug as randaug_draws
+from .clip_ops import GpuClipLoader, GpuLabelledLoader, assemble_batch, assemble_pairs, augment_settings
 
 MAX_DECODE_THREADS = 16
 
@@ -219,8 +220,11 @@ class _FolderSource:
     def __len__(self):
         return len(self.data)
 
+    def _seed(self, index: int, epoch: int) -> int:
+        return ((self.seed * 1000003 + epoch) * 1000003 + index) * 101 + self._SALT[self.data_type]
+
     def _rngs(self, index: int, epoch: int):
-        s = ((self.seed * 1000003 + epoch) * 1000003 + index) * 101 + self._SALT[self.data_type]
+        s = self._seed(index, epoch)
         return random.Random(s), np.random.RandomState(s & 0x7fffffff)
 
     # -- staging ----------------------------------------------------------------------------------------------------------
@@ -330,11 +334,15 @@ class FrameLabelledFolder(_FolderSource):
     do, from the JPEG frames of the listed videos, under the PIL transform modes 'img' / 'img_val' / 'img_test' (the ``numpy*``
     modes resize with cv2 and stay refused).  The label is the list's second column as it stands (datasets.py:977).
     ``list_from="train"`` with data_type 'test' / mode 'img_test' reads the TRAIN list as whole-video test items: the gallery of
-    nearest-neighbour retrieval (cstp_amd.retrieval); by default the list follows data_type."""
+    nearest-neighbour retrieval (cstp_amd.retrieval); by default the list follows data_type.  ``randaug=(n, m, mstd)`` and
+    ``random_erase=P`` augment 'train' clips (cstp_amd.randaug), from a generator of their own per clip."""
+
+    augment = None
 
     def __init__(self, device, frame_dir, annotation_path, split=1, data_type="train", mode="img", sample_duration=16,
-                 sample_size=112, pb_rate=4, seed=1, n_workers=4, list_from=None):
+                 sample_size=112, pb_rate=4, seed=1, n_workers=4, list_from=None, randaug=None, random_erase=0.0):
         sampler._check_ft_mode(mode)
+        self.augment = augment_settings(randaug, random_erase, data_type, mode)      # training clips only
         if (data_type == "test") != (mode == "img_test"):
             raise ValueError("data_type %r with transform mode %r: the video test takes 'img_test', train / val take 'img' / "
                              "'img_val'" % (data_type, mode))
@@ -360,7 +368,10 @@ class FrameLabelledFolder(_FolderSource):
         first = sampler.ft_clip_frames(n_frames, self.t, self.pb_rate, rng)[0]
         rng.setstate(state)
         w, h = frame_size(frame_path(folder, first))
-        return sampler.sample_ft_clip(n_frames, w, h, self.t, self.size, self.pb_rate, self.mode, rng), w, h
+        plan = sampler.sample_ft_clip(n_frames, w, h, self.t, self.size, self.pb_rate, self.mode, rng)
+        if self.augment is not None:      # a generator of its own: the draws above keep their values
+            plan.randaug, plan.erase = randaug_draws.draw(self.augment, self.size, randaug_draws.clip_rng(self._seed(index, epoch)))
+        return plan, w, h
 
     def plan(self, index: int, epoch: int = 0):
         return self.plan_sized(index, epoch)[0]
@@ -439,7 +450,12 @@ def build_pretrain(opts, device) -> FramePairFolder:
                            opts.sample_size, opts.manual_seed, opts.n_workers)
 
 
-def build_finetune(opts, device, data_type: str, mode: str, list_from=None) -> FrameLabelledFolder:
-    """--dataset UcfFineTune from the reference's flags, for 'train' / 'val' / 'test' under ``mode``."""
+def build_finetune(opts, device, data_type: str, mode: str, list_from=None, augment=None) -> FrameLabelledFolder:
+    """--dataset UcfFineTune from the reference's flags, for 'train' / 'val' / 'test' under ``mode``.  ``augment``: the
+    ``randaug.Settings`` of --randaug_* / --random_erase, honoured for 'train' only."""
+    if data_type != "train":
+        augment = None
     return FrameLabelledFolder(device, opts.frame_dir, opts.annotation_path, opts.split, data_type, mode, opts.sample_duration,
-                               opts.sample_size, opts.pb_rate, opts.manual_seed, opts.n_workers, list_from)
+                               opts.sample_size, opts.pb_rate, opts.manual_seed, opts.n_workers, list_from,
+                               randaug=None if augment is None else (augment.n, augment.m, augment.mstd),
+                               random_erase=0.0 if augment is None else augment.erase)

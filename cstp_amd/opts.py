@@ -31,6 +31,15 @@ Additions (all optional, defaults reproduce the reference):
   --drop_path        fine-tuning: stochastic depth on the residual blocks of r21d_byol / r3d_byol, in [0, 1) (default 0 = off):
                      block l of L is dropped per sample with P * l / (L - 1); refused for s3d_byol, i3d_byol and --task ft_fc
                      (cstp_amd/regularize.py; validation, main_byol.py, test.py, retrieval.py and knn.py never regularise)
+  --randaug_n        fine-tuning: RandAugment operations per TRAINING clip, 0..4 (default 0 = off), drawn uniformly from the 14 of
+                     the paper; each equals its Pillow call bit for bit on every frame, fill colour (128, 128, 128)
+  --randaug_m        its magnitude m, a float in [0, 30] (default 9)
+  --randaug_mstd     each operation's magnitude is min(30, max(0, gauss(m, mstd))), >= 0 (default 0)
+  --random_erase     fine-tuning: probability in [0, 1] that a training clip gets one box, through all its frames, erased to
+                     uniform noise on [-1, 1) (default 0 = off)
+                     (cstp_amd/randaug.py, csrc/randaug.h: one operation table per layer for the whole batch; --dataset
+                     synthetic_video | UcfFineTune with --transform_mode img only, refused otherwise; validation and test clips
+                     are never augmented; every driver but main_ft_mp.py ignores all four)
   --knn_k           weighted k-NN classification (knn.py, the --knn_every monitor): neighbours per query, 1..64 (default 20)
   --knn_t           its temperature: neighbour j weighs exp((sim_j - sim_0) / T), must be > 0 (default 0.07)
   --knn_every       main_byol.py: after every E-th epoch and after the last, rank 0 classifies the labelled test videos by k-NN
@@ -144,6 +153,10 @@ _FLAGS = [
     ("mix_switch_prob", 0.5, float, "main_ft_mp.py: probability of CutMix instead of mixup when both alphas are positive"),
     ("dropout", 0.0, float, "main_ft_mp.py: dropout probability in front of the classifier, in [0, 1) (0 = off)"),
     ("drop_path", 0.0, float, "main_ft_mp.py: stochastic depth on the residual blocks of r21d_byol / r3d_byol, linear rule, in [0, 1) (0 = off)"),
+    ("randaug_n", 0, int, "main_ft_mp.py: RandAugment operations per training clip, 0..4 (0 = off)"),
+    ("randaug_m", 9.0, float, "main_ft_mp.py: RandAugment magnitude, in [0, 30]"),
+    ("randaug_mstd", 0.0, float, "main_ft_mp.py: standard deviation of the per-operation magnitude gauss(m, mstd) clipped to [0, 30], >= 0"),
+    ("random_erase", 0.0, float, "main_ft_mp.py: probability in [0, 1] that a training clip gets a box erased to noise (0 = off)"),
     ("knn_every", 0, int, "main_byol.py: k-NN top-1 of the online encoder after every E-th epoch and after the last (0 = off)"),
 ]
 RETRIEVAL_MAX_K = 64      # ops.SIM_TOPK_MAX_K: one lane per list slot

@@ -222,6 +222,8 @@ class FtClipPlan:
     window: Tuple[int, int]                    # (x, y) origin of the size x size output window in the resized image
     jitter: Optional[List[Tuple[str, float]]] = None   # ClipColorJitter's operations in shuffled order, or None
     flip: bool = False                         # 'img' has no flip (preprocess_data.py:1135 is commented out)
+    randaug: Optional[List[Tuple[str, float]]] = None   # RandAugment: (operation, parameter of its Pillow call) per layer, or None
+    erase: Optional[Tuple[int, int, int, int, int]] = None   # random erasing: (x0, y0, w, h, 64-bit fill key) or None (cstp_amd.randaug)
 
 
 def _wrap_indices(total_frames: int, sample_duration: int, pb_rate: int, first: int) -> List[int]:

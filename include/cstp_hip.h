@@ -464,6 +464,47 @@ typedef struct cstp_clip_mix_entry {
 int cstp_clip_mix(void* stream, const float* x, float* y, const cstp_clip_mix_entry* table, int32_t b, int32_t planes, int32_t h,
                   int32_t w);
 
+/* ---- RandAugment and random erasing on a batch of 8-bit clips (fine-tuning; csrc/randaug.h; no reference
+ * counterpart).  Clips are square: uint8 [b][t][s][s][3].  Every operation equals the Pillow call it stands for bit for bit, on
+ * every frame, with the fill colour (128, 128, 128).
+ * cstp_randaug_layer applies ONE operation per clip, src -> dst (dst must not alias src), read from a table with one entry per
+ * clip; at most two launches whatever b is:
+ *   op 0  copy
+ *   op 1  ImageOps.autocontrast        op 2  ImageOps.equalize     (per frame and channel: histograms -> look-up tables)
+ *   op 3  ImageOps.posterize: v & a[0]                              (a[0] = ~(2^(8 - bits) - 1) & 255)
+ *   op 4  ImageOps.solarize: v < a[0] ? v : 255 - v
+ *   op 5  ImageEnhance.Brightness      op 6  ImageEnhance.Contrast  op 7  ImageEnhance.Color   op 8  ImageEnhance.Sharpness
+ *         = Image.blend(degenerate, image, factor) against black / the frame's mean luma / the pixel's luma / the 3x3
+ *         ImageFilter.SMOOTH of the frame; single precision without fused multiply-add, as cstp_clip_blend
+ *   op 9  Image.transform(AFFINE, NEAREST, fillcolor) / Image.rotate(fillcolor): Geometry.c affine_fixed with the six 16.16
+ *         fixed-point coefficients a[0..5] (as cstp_clip_rotate's coef6), the fill colour outside the frame
+ *   op 10 integer translation: out(x, y) = in(x + a[0], y + a[1]), the fill colour outside the frame
+ * lut: device uint8 [b][t][3][256], mean: device int32 [b][t] -- scratch of the statistics launch, which runs only when some
+ * entry holds op 1, 2 or 6 (both may be NULL otherwise); nothing is read back.  table_host is the same table in host memory,
+ * read only during the call to check every entry before anything is launched.  b <= 65535, s <= 4096, t*s*s*3 < 2^31.
+ * cstp_randaug_finish is cstp_clip_finish for the whole batch in one launch: clip i of src -> out[out_slot] (fp32
+ * [out_slots][3][t][s][s]) with [FLIP_LEFT_RIGHT] -> ToTensor -> x * 2 - 1 clamped.  A box with w, h > 0 -- in OUTPUT coordinates,
+ * after the flip, through all frames and channels -- is erased on the way out: element e of the clip's fp32 tensor inside it
+ * becomes (word >> 8) * 2^-23 - 1 (uniform on [-1, 1)), word = Philox4x32-10(counter (e >> 2, 0), key)[e & 3], the counter layout
+ * of cstp_dropout with offset 0. */
+typedef struct cstp_randaug_entry {
+  int32_t op;              /* 0..10, see above */
+  int32_t a[6];            /* fixed-point coefficients / shift / mask / threshold */
+  float factor;            /* blend factor of ops 5..8 */
+} cstp_randaug_entry;
+typedef struct cstp_randaug_finish_entry {
+  int32_t out_slot;        /* clip index in out */
+  int32_t flip;            /* FLIP_LEFT_RIGHT folded into the store */
+  int32_t x0, y0, w, h;    /* erased box in the output frame; w = h = 0: none */
+  uint32_t key_lo, key_hi; /* the 64-bit Philox key of the fill */
+} cstp_randaug_finish_entry;
+/* sizeof(cstp_randaug_entry) == sizeof(cstp_randaug_finish_entry), for callers that pack the tables without this header. */
+size_t cstp_randaug_entry_bytes(void);
+int cstp_randaug_layer(void* stream, const uint8_t* src, uint8_t* dst, const cstp_randaug_entry* table_dev,
+                       const cstp_randaug_entry* table_host, int32_t b, int32_t t, int32_t s, uint8_t* lut, int32_t* mean);
+int cstp_randaug_finish(void* stream, const uint8_t* src, float* out, const cstp_randaug_finish_entry* table_dev,
+                        const cstp_randaug_finish_entry* table_host, int32_t b, int32_t t, int32_t s, int32_t out_slots);
+
 /* ---- per-step utilities over FLAT parameter arenas -------------------------------------- */
 /* EMA r21d_byol.py:331-337: target = target*m + online*(1-m) over n floats. */
 int cstp_ema_update(void* stream, float* target, const float* online, size_t n, double m);

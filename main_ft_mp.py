@@ -27,7 +27,9 @@ What is added (off by default, then the step is the one above): --label_smoothin
 --mix_switch_prob regularise TRAINING with smoothed / mixed targets and blended clips (cstp_amd.mix, cstp_clip_mix,
 cstp_soft_cross_entropy_*); training accuracy is then taken against the target that carried the larger weight.  --dropout and
 --drop_path add dropout in front of the classifier and stochastic depth on the residual blocks (cstp_amd.regularize, cstp_dropout,
-cstp_droppath_add_relu_*), in training forwards only.
+cstp_droppath_add_relu_*), in training forwards only.  --randaug_n / --randaug_m / --randaug_mstd and --random_erase augment the
+TRAINING clips of --dataset synthetic_video | UcfFineTune under --transform_mode img with RandAugment and random erasing on the
+8-bit frames of the whole batch (cstp_amd.randaug, cstp_randaug_layer / cstp_randaug_finish); validation clips never are.
 """
 from __future__ import annotations
 
@@ -40,7 +42,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from cstp_amd import ops
+from cstp_amd import ops, randaug
 from cstp_amd.mix import build_mixer
 from cstp_amd.model import generate_model
 from cstp_amd.optim import build_optimizer
@@ -63,7 +65,10 @@ def reduce_mean(tensor, world_size):
     return rt
 
 
-def build_dataset(opts, data_type):
+def build_dataset(opts, data_type, augment=None):
+    """``augment``: the randaug.Settings of --randaug_* / --random_erase (None = off); training clips only."""
+    if data_type != "train":
+        augment = None
     if opts.dataset == "synthetic_video":
         # labelled uint8 videos in HBM; train clips take --transform_mode ('img'), validation '{}_val'.format(mode) (:80,93)
         from cstp_amd.clip_ops import GpuLabelledVideos
@@ -71,12 +76,14 @@ def build_dataset(opts, data_type):
         length = opts.synthetic_len if data_type == "train" else max(opts.synthetic_len // 4, 1)
         return GpuLabelledVideos(torch.device("cuda", opts.device), data_type, mode, n_classes=opts.n_classes,
                                  sample_duration=opts.sample_duration, sample_size=opts.sample_size, pb_rate=opts.pb_rate,
-                                 length=length, seed=opts.manual_seed)
+                                 length=length, seed=opts.manual_seed,
+                                 randaug=None if augment is None else (augment.n, augment.m, augment.mstd),
+                                 random_erase=0.0 if augment is None else augment.erase)
     if opts.dataset == "UcfFineTune":
         # frame folders listed under --annotation_path; the same modes, the JPEGs decoded on CPU threads
         from cstp_amd.frame_folder import build_finetune
         mode = opts.transform_mode if data_type == "train" else "{}_val".format(opts.transform_mode)
-        return build_finetune(opts, torch.device("cuda", opts.device), data_type, mode)
+        return build_finetune(opts, torch.device("cuda", opts.device), data_type, mode, augment=augment)
     if opts.dataset != "synthetic":
         raise NotImplementedError("dataset %r: --dataset synthetic, synthetic_video and UcfFineTune (UCF-style frame folders) are "
                                   "built in (the reference's Kinetics / LMDB readers are outside this package's scope)"
@@ -202,9 +209,10 @@ def main_worker(local_rank, opts):
     if opts.task not in TRAIN_TASKS:
         raise ValueError("main_ft_mp.py serves --task %s, got %r" % ("/".join(TRAIN_TASKS), opts.task))
     regularizer = build_regularizer(opts)        # --dropout / --drop_path: refused here, before any data or model is built
+    augment = randaug.from_opts(opts)            # --randaug_* / --random_erase likewise; None at the defaults
 
     print("Preprocessing train data ...")
-    train_data = build_dataset(opts, "train")
+    train_data = build_dataset(opts, "train", augment)
     len_train_data = len(train_data)
     print("Length of training data = ", len_train_data)
     train_dataloader, train_sampler = build_dataloader(train_data, opts, "train")
