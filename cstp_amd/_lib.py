@@ -155,6 +155,9 @@ SIGNATURES = {
     "cstp_lars_workspace_bytes": (c_size_t, [c_int32]),
     "cstp_lars_ratio": (c_int32, [_P, _P, _P, c_size_t, _P, c_int32, _P, c_int32, c_float, c_float, _P, _P, _P, c_size_t]),
     "cstp_lars_step": (c_int32, [_P, _P, _P, _P, c_size_t, _P, c_int32, _P, c_int32, _P, _P, c_float, c_float, _P, c_int32]),
+    "cstp_tab_sgd_step": (c_int32, [_P, _P, _P, _P, _P, c_size_t, _P, c_int32, _P, c_int32, _P, c_float, _P, c_int32, c_int32, c_float]),
+    "cstp_tab_adam_step": (c_int32, [_P, _P, _P, _P, _P, _P, c_size_t, _P, c_int32, _P, c_int32, _P, c_float, c_float, c_float, c_int32,
+                                     c_int32, c_float]),
     # the bf16-storage path (csrc/b16.hip)
     "cstp_b16_cast": (c_int32, [_P, _P, _P, c_size_t]),
     "cstp_b16_conv3d_workspace_bytes": (c_size_t, [POINTER(ConvDesc)]),

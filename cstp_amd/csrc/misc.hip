@@ -561,4 +561,5 @@ extern "C" int cstp_maxpool3d_backward(void* stream, const float* dy, const int3
 }
 
 #include "lars.h"
+#include "optim_table.h"
 #include "reg.h"

@@ -168,7 +168,11 @@ def generate_model(opts):
         print("Test model {}!".format(opts.test_md_path))
         test_md = _load_checkpoint(opts.test_md_path, device)
         assert opts.arch == test_md["arch"]
-        model.load_state_dict(test_md["state_dict"])
+        key = "state_dict_ema" if getattr(opts, "test_ema", 0) else "state_dict"      # --test_ema 1: the EMA weights
+        if key not in test_md:
+            raise ValueError("--test_ema 1: checkpoint %s holds no state_dict_ema (it was not written under --model_ema)"
+                             % (opts.test_md_path,))
+        model.load_state_dict(test_md[key])
         return model
     if opts.task == "resume":
         print("Resume model {}!".format(opts.resume_md_path))

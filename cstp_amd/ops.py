@@ -2367,6 +2367,39 @@ def lars_step_(p, g, buf, chunks, segs, ratio, lr: torch.Tensor, momentum: float
                              float(weight_decay), _ptr(coef), 1 if write_back_grad else 0), "cstp_lars_step")
 
 
+def _tab_tables(chunks: torch.Tensor, hyper: torch.Tensor, arenas) -> None:
+    if chunks.dtype != torch.int32 or chunks.dim() != 2 or chunks.shape[1] != 3 or not chunks.is_contiguous() or not chunks.is_cuda:
+        raise _lib.CstpError("table-step chunks table must be a contiguous int32 [n, 3] tensor on a HIP device")
+    if hyper.dtype != torch.float32 or hyper.dim() != 2 or hyper.shape[1] != 2 or not hyper.is_contiguous() or not hyper.is_cuda:
+        raise _lib.CstpError("table-step hyper table must be a contiguous float32 [n_tensors, 2] tensor on a HIP device")
+    n = arenas[0].numel()
+    for a in arenas:
+        if a is not None and (a.dtype != torch.float32 or a.numel() != n or not a.is_contiguous() or a.device != chunks.device):
+            raise _lib.CstpError("table-step arenas must be contiguous float32 tensors of one length on the tables' device")
+
+
+def tab_sgd_step_(p, g, buf, chunks, hyper, lr: torch.Tensor, momentum: float, coef: Optional[torch.Tensor], first_step: bool,
+                  write_back_grad: bool = True, ema: Optional[torch.Tensor] = None, ema_momentum: float = 0.0) -> None:
+    """cstp_tab_sgd_step: the SGD update of every chunk with its tensor's {lr scale, weight decay} (``hyper``), and with ``ema`` the
+    shadow update ema = m * ema + (1 - m) * p in the same launch; p, g, buf, ema are the WHOLE arenas."""
+    lib = _lib.load()
+    _tab_tables(chunks, hyper, (p, g, buf, ema))
+    check(lib.cstp_tab_sgd_step(_stream(), p.data_ptr(), g.data_ptr(), buf.data_ptr(), _ptr(ema), p.numel(), chunks.data_ptr(),
+                                chunks.shape[0], hyper.data_ptr(), hyper.shape[0], lr.data_ptr(), float(momentum), _ptr(coef),
+                                1 if first_step else 0, 1 if write_back_grad else 0, float(ema_momentum)), "cstp_tab_sgd_step")
+
+
+def tab_adam_step_(p, g, exp_avg, exp_avg_sq, chunks, hyper, lr: torch.Tensor, beta1: float, beta2: float, eps: float,
+                   decoupled: bool, step: int, ema: Optional[torch.Tensor] = None, ema_momentum: float = 0.0) -> None:
+    """cstp_tab_adam_step: Adam (coupled decay) / AdamW (decoupled) likewise; ``step`` counts from 1."""
+    lib = _lib.load()
+    _tab_tables(chunks, hyper, (p, g, exp_avg, exp_avg_sq, ema))
+    check(lib.cstp_tab_adam_step(_stream(), p.data_ptr(), g.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), _ptr(ema),
+                                 p.numel(), chunks.data_ptr(), chunks.shape[0], hyper.data_ptr(), hyper.shape[0], lr.data_ptr(),
+                                 float(beta1), float(beta2), float(eps), 1 if decoupled else 0, int(step), float(ema_momentum)),
+          "cstp_tab_adam_step")
+
+
 def adam_step_(p, g, exp_avg, exp_avg_sq, lr: torch.Tensor, beta1: float, beta2: float, eps: float, weight_decay: float,
                decoupled: bool, step: int) -> None:
     lib = _lib.load()

@@ -11,6 +11,10 @@ flat parameter/gradient arenas instead of ~170 x 3 tiny launches:
     (pre-training / ft_all / scratch: one run = the whole arena; ft_fc: one run = classify.weight|bias).
 FlatLARS (--optimizer lars) is the one optimizer here the reference does not have: per-tensor trust ratios need a reduction per
 tensor, which three launches per run over chunk tables do (csrc/lars.h).
+TableSGD / TableAdam (fine-tuning's --layer_decay / --wd_skip_1d / --model_ema, cstp_amd/recipe.py) are FlatSGD / FlatAdam for
+hyper-parameters that differ from tensor to tensor: a learning-rate scale and a weight decay per tensor would make almost every
+tensor its own run, so their kernel looks both up per block in a table over the same chunks (csrc/optim_table.h) and the step stays
+ONE launch whatever the grouping; the weight EMA of enable_ema() is updated in that launch too.
 """
 from __future__ import annotations
 
@@ -56,6 +60,42 @@ class _FlatOptimizer(torch.optim.Optimizer):
         self._coef = torch.ones(1, dtype=torch.float32, device=self._p.device)
         self._norm = torch.zeros(1, dtype=torch.float32, device=self._p.device)
         self._clip_pending = False
+        # --model_ema (enable_ema): shadows of the parameter arena and of the float BatchNorm-buffer arena; None = off
+        self._buffers = arenas.get("buffers")
+        self._ema, self._ema_buffers = None, None
+        self._ema_momentum, self._ema_updates = 0.0, 0
+
+    # -- exponential moving average of the weights (fine-tuning's --model_ema) -----------------------------------------------------
+    @torch.no_grad()
+    def enable_ema(self, momentum: float) -> None:
+        """From now on every step() also moves a shadow of the parameter arena and of the float BatchNorm-buffer arena towards the
+        weights: shadow <- m * shadow + (1 - m) * value with m = ema_momentum_at(momentum, t) at the t-th update.  The shadows
+        start as copies, so call this after the checkpoint has been loaded.  Frozen tensors are never touched: their shadow stays
+        the copy.  TableSGD / TableAdam update the parameter shadow inside their step kernel; the other classes run one
+        ops.ema_update_ per run of _plan() after theirs."""
+        momentum = float(momentum)
+        if not 0.0 <= momentum < 1.0:
+            raise ValueError("EMA momentum must lie in [0, 1), got %r" % (momentum,))
+        self._ema = self._p.clone()
+        self._ema_buffers = self._buffers.clone() if self._buffers is not None and self._buffers.numel() > 0 else None
+        self._ema_momentum, self._ema_updates = momentum, 0
+
+    def _next_ema_momentum(self) -> float:
+        self._ema_updates += 1
+        return ema_momentum_at(self._ema_momentum, self._ema_updates)
+
+    def _ema_buffer_pass(self, m: float) -> None:
+        if self._ema_buffers is not None:
+            ops.ema_update_(self._ema_buffers, self._buffers, m)
+
+    def _ema_separate_pass(self) -> None:
+        """The shadow update as its own pass over the trainable runs (the classes whose step kernel does not carry it)."""
+        if self._ema is None:
+            return
+        m = self._next_ema_momentum()
+        for off, n, _, _ in self._plan():
+            ops.ema_update_(self._ema[off:off + n], self._p[off:off + n], m)
+        self._ema_buffer_pass(m)
 
     # main_byol.py:86 / main_ft_mp.py:210 -- gradients are arena views, so "zero" (not set-to-None) keeps them in place
     def zero_grad(self, set_to_none: bool = False):
@@ -100,6 +140,57 @@ class _FlatOptimizer(torch.optim.Optimizer):
         return runs
 
 
+# checkpoint wire formats shared by the classes below: torch.optim.SGD's (momentum_buffer) and torch.optim.Adam / AdamW's
+# (step, exp_avg, exp_avg_sq), one state entry per trainable tensor that has taken a step, indexed as torch indexes them
+def _sgd_state(opt):
+    state = {}
+    for i, (_, off, _, numel, p) in enumerate(opt._slots):
+        if opt._steps > 0 and p.requires_grad and off >= 0:
+            state[i] = {"momentum_buffer": opt._buf[off:off + numel].view_as(p).clone()}
+    return state
+
+
+def _load_sgd_state(opt, sd, keys):
+    loaded = False
+    for i, (_, off, _, numel, p) in enumerate(opt._slots):
+        st = sd["state"].get(i, sd["state"].get(str(i)))
+        if st is not None and st.get("momentum_buffer") is not None and off >= 0:
+            opt._buf[off:off + numel].view_as(p).copy_(st["momentum_buffer"])
+            loaded = True
+    opt._steps = 1 if loaded else 0
+    _load_group_keys(opt, sd, keys)
+
+
+def _adam_state(opt):
+    state = {}
+    for i, (_, off, _, numel, p) in enumerate(opt._slots):
+        if opt._steps > 0 and p.requires_grad and off >= 0:
+            state[i] = {"step": torch.tensor(float(opt._steps)),
+                        "exp_avg": opt._m[off:off + numel].view_as(p).clone(),
+                        "exp_avg_sq": opt._v[off:off + numel].view_as(p).clone()}
+    return state
+
+
+def _load_adam_state(opt, sd, keys):
+    steps = 0
+    for i, (_, off, _, numel, p) in enumerate(opt._slots):
+        st = sd["state"].get(i, sd["state"].get(str(i)))
+        if st is not None and "exp_avg" in st and off >= 0:
+            opt._m[off:off + numel].view_as(p).copy_(st["exp_avg"])
+            opt._v[off:off + numel].view_as(p).copy_(st["exp_avg_sq"])
+            steps = max(steps, int(float(st.get("step", 0))))
+    opt._steps = steps
+    _load_group_keys(opt, sd, keys)
+
+
+def _load_group_keys(opt, sd, keys):
+    for g, sg in zip(opt.param_groups, sd["param_groups"]):
+        for k in keys:
+            if k in sg:
+                g[k] = tuple(sg[k]) if k == "betas" else sg[k]
+
+
+
 class FlatSGD(_FlatOptimizer):
     """Drop-in for ``optim.SGD(parameters, lr, momentum, weight_decay)`` on a model whose parameters were
     re-homed by ``R21DBYOL.flatten_parameters()``; ``params`` may be ``model.parameters()`` or the per-tensor
@@ -129,25 +220,11 @@ class FlatSGD(_FlatOptimizer):
     # checkpoint wire format of torch.optim.SGD (main_byol.py:132-140 saves optimizer.state_dict())
     def state_dict(self):
         sd = super().state_dict()
-        state = {}
-        for i, (_, off, _, numel, p) in enumerate(self._slots):
-            if self._steps > 0 and p.requires_grad and off >= 0:
-                state[i] = {"momentum_buffer": self._buf[off:off + numel].view_as(p).clone()}
-        sd["state"] = state
+        sd["state"] = _sgd_state(self)
         return sd
 
     def load_state_dict(self, sd):
-        loaded = False
-        for i, (_, off, _, numel, p) in enumerate(self._slots):
-            st = sd["state"].get(i, sd["state"].get(str(i)))
-            if st is not None and st.get("momentum_buffer") is not None and off >= 0:
-                self._buf[off:off + numel].view_as(p).copy_(st["momentum_buffer"])
-                loaded = True
-        self._steps = 1 if loaded else 0
-        for g, sg in zip(self.param_groups, sd["param_groups"]):
-            for k in ("lr", "momentum", "weight_decay"):
-                if k in sg:
-                    g[k] = sg[k]
+        _load_sgd_state(self, sd, ("lr", "momentum", "weight_decay"))
 
 
 class FlatAdam(_FlatOptimizer):
@@ -179,28 +256,11 @@ class FlatAdam(_FlatOptimizer):
 
     def state_dict(self):
         sd = super().state_dict()
-        state = {}
-        for i, (_, off, _, numel, p) in enumerate(self._slots):
-            if self._steps > 0 and p.requires_grad and off >= 0:
-                state[i] = {"step": torch.tensor(float(self._steps)),
-                            "exp_avg": self._m[off:off + numel].view_as(p).clone(),
-                            "exp_avg_sq": self._v[off:off + numel].view_as(p).clone()}
-        sd["state"] = state
+        sd["state"] = _adam_state(self)
         return sd
 
     def load_state_dict(self, sd):
-        steps = 0
-        for i, (_, off, _, numel, p) in enumerate(self._slots):
-            st = sd["state"].get(i, sd["state"].get(str(i)))
-            if st is not None and "exp_avg" in st and off >= 0:
-                self._m[off:off + numel].view_as(p).copy_(st["exp_avg"])
-                self._v[off:off + numel].view_as(p).copy_(st["exp_avg_sq"])
-                steps = max(steps, int(float(st.get("step", 0))))
-        self._steps = steps
-        for g, sg in zip(self.param_groups, sd["param_groups"]):
-            for k in ("lr", "betas", "eps", "weight_decay"):
-                if k in sg:
-                    g[k] = tuple(sg[k]) if k == "betas" else sg[k]
+        _load_adam_state(self, sd, ("lr", "betas", "eps", "weight_decay"))
 
 
 def lars_tables(slots, chunk):
@@ -276,6 +336,7 @@ class FlatLARS(_FlatOptimizer):
                            g["weight_decay"], coef, True)
         self._clip_pending = False
         self._steps += 1
+        self._ema_separate_pass()      # --model_ema: its own pass here (the LARS kernels carry no shadow)
 
     def trust_ratios(self):
         """-> (q [n_tensors] on the device, parameter indices [n_tensors]): the trust ratio each tensor took in the last step, in
@@ -290,25 +351,200 @@ class FlatLARS(_FlatOptimizer):
     # checkpoint wire format of torch.optim.SGD, as FlatSGD writes it (main_byol.py:132-140 saves optimizer.state_dict())
     def state_dict(self):
         sd = super().state_dict()
-        state = {}
-        for i, (_, off, _, numel, p) in enumerate(self._slots):
-            if self._steps > 0 and p.requires_grad and off >= 0:
-                state[i] = {"momentum_buffer": self._buf[off:off + numel].view_as(p).clone()}
-        sd["state"] = state
+        sd["state"] = _sgd_state(self)
         return sd
 
     def load_state_dict(self, sd):
-        loaded = False
-        for i, (_, off, _, numel, p) in enumerate(self._slots):
-            st = sd["state"].get(i, sd["state"].get(str(i)))
-            if st is not None and st.get("momentum_buffer") is not None and off >= 0:
-                self._buf[off:off + numel].view_as(p).copy_(st["momentum_buffer"])
-                loaded = True
-        self._steps = 1 if loaded else 0
-        for g, sg in zip(self.param_groups, sd["param_groups"]):
-            for k in ("lr", "momentum", "weight_decay", "eta"):
-                if k in sg:
-                    g[k] = sg[k]
+        _load_sgd_state(self, sd, ("lr", "momentum", "weight_decay", "eta"))
+
+
+def ema_momentum_at(momentum: float, t: int) -> float:
+    """Momentum of the t-th shadow update, t counted from 1: min(momentum, (1 + t) / (10 + t)) -- early updates follow the weights
+    closely (2/11, 3/12, ...) instead of averaging in the initial values for 1 / (1 - momentum) steps."""
+    if t < 1:
+        raise ValueError("EMA updates are counted from 1, got %r" % (t,))
+    return min(float(momentum), (1.0 + t) / (10.0 + t))
+
+
+def hyper_tables(slots, chunk):
+    """The tables of csrc/optim_table.h for the trainable tensors ``slots`` = [(offset, numel, lr scale, weight decay)] of one arena:
+    the chunk table of lars_tables (chunks never cross a tensor; offsets and lengths are multiples of 4; frozen tensors are simply
+    not listed) and one {lr scale, weight decay} row per tensor.
+      -> chunks [(segment, offset, length)], hyper [(lr scale, weight decay)], segment s being slots[s].  Pure host code."""
+    chunks, _ = lars_tables([(off, numel, False) for off, numel, _, _ in slots], chunk)
+    hyper = []
+    for s, (_, _, scale, wd) in enumerate(slots):
+        scale, wd = float(scale), float(wd)
+        if not (scale >= 0.0 and scale < float("inf")) or not (wd >= 0.0 and wd < float("inf")):
+            raise ValueError("tensor %d: lr scale %r / weight decay %r (both finite and >= 0)" % (s, scale, wd))
+        hyper.append((scale, wd))
+    return chunks, hyper
+
+
+class _TableOptimizer(_FlatOptimizer):
+    """What TableSGD and TableAdam share: ONE launch per step whatever the grouping (csrc/optim_table.h).
+
+    Each group may carry ``lr_scale`` (default 1) and its own ``weight_decay``; ``param_groups[i]["lr"]`` holds
+    ``base * lr_scale``, so a scheduler that multiplies every group (ReduceLROnPlateau) or sets ``value * lr_scale`` per group
+    (recipe.WarmupCosine) and the drivers' log line keep working.  step() derives the base rate from the groups and refuses groups
+    that disagree on it.  The base lives in one persistent device scalar, refreshed with ``fill_`` when its value changes, and the
+    scales in a static device table: a change of learning rate costs no table rebuild, no allocation and no host read.  The
+    tables are rebuilt only when a group's lr_scale / weight_decay or a tensor's requires_grad changes.
+    _plan() merges arena-adjacent TRAINABLE tensors regardless of hyper-parameters, so FineTuneStep's per-run all-reduce stays one
+    collective per contiguous trainable run."""
+
+    BASE_RTOL = 1e-6        # group lr against base * lr_scale: products of doubles taken in different orders
+
+    def __init__(self, params, defaults, arenas):
+        defaults = dict(defaults, lr_scale=1.0)
+        super().__init__(params, defaults, arenas)
+        if self._p.numel() >= 1 << 31:
+            raise ValueError("%s: the arena holds %d floats; the chunk tables hold int32 offsets (< 2^31)"
+                             % (type(self).__name__, self._p.numel()))
+        for g in self.param_groups:
+            if not (float(g["lr_scale"]) >= 0.0):
+                raise ValueError("lr_scale must be >= 0, got %r" % (g["lr_scale"],))
+            g["lr"] = float(g["lr"]) * float(g["lr_scale"])
+        self._lr_dev = torch.zeros(1, dtype=torch.float32, device=self._p.device)
+        self._lr_base = None
+        self._tables_key, self._tables = None, None
+
+    def _live(self):
+        """Slot indices of the trainable tensors in arena order."""
+        return [i for _, i in sorted((s[1], i) for i, s in enumerate(self._slots) if s[1] >= 0 and s[4].requires_grad)]
+
+    def _plan(self):
+        """Runs of arena-adjacent trainable tensors, whatever their hyper-parameters: [(offset, length, first group, None)]."""
+        key = tuple(s[4].requires_grad for s in self._slots)
+        if key == self._runs_key:
+            return self._runs
+        runs = []
+        for i in self._live():
+            gi, off, plen, _, _ = self._slots[i]
+            if runs and runs[-1][0] + runs[-1][1] == off:
+                runs[-1][1] += plen
+            else:
+                runs.append([off, plen, self.param_groups[gi], None])
+        self._runs_key, self._runs = key, runs
+        return runs
+
+    def _step_tables(self):
+        """(chunks, hyper) on the device, rebuilt when a scale, a decay or the set of trainable tensors changes."""
+        live = self._live()
+        key = tuple((i, float(self.param_groups[self._slots[i][0]]["lr_scale"]),
+                     float(self.param_groups[self._slots[i][0]]["weight_decay"])) for i in live)
+        if key != self._tables_key:
+            if not live:
+                raise ValueError("%s: no trainable tensor in the arena" % type(self).__name__)
+            chunks, hyper = hyper_tables([(self._slots[i][1], self._slots[i][3], sc, wd) for i, sc, wd in key], ops.LARS_CHUNK)
+            dev = self._p.device
+            self._tables = (torch.tensor(chunks, dtype=torch.int32, device=dev), torch.tensor(hyper, dtype=torch.float32, device=dev))
+            self._tables_key = key
+        return self._tables
+
+    def base_lr(self) -> float:
+        """The base rate the groups of the trainable tensors agree on: lr == base * lr_scale in every one of them."""
+        groups = [self.param_groups[gi] for gi in sorted({self._slots[i][0] for i in self._live()})]
+        lead = max(groups, key=lambda g: float(g["lr_scale"]), default=None)
+        if lead is None or float(lead["lr_scale"]) == 0.0:
+            return 0.0
+        base = float(lead["lr"]) / float(lead["lr_scale"])
+        for g in groups:
+            want = base * float(g["lr_scale"])
+            if abs(float(g["lr"]) - want) > self.BASE_RTOL * abs(want):
+                raise ValueError("%s: a group's lr is %r where base %r * lr_scale %r = %r: set every group's lr to base * lr_scale "
+                                 "(the learning-rate decay per layer lives in lr_scale)"
+                                 % (type(self).__name__, g["lr"], base, g["lr_scale"], want))
+        return base
+
+    def _lr_scalar(self) -> torch.Tensor:
+        base = self.base_lr()
+        if base != self._lr_base:
+            self._lr_dev.fill_(base)
+            self._lr_base = base
+        return self._lr_dev
+
+    def _ema_args(self):
+        """(shadow arena or None, momentum of this update) for the step kernel; the buffer shadow takes its own small pass."""
+        if self._ema is None:
+            return None, 0.0
+        m = self._next_ema_momentum()
+        self._ema_buffer_pass(m)
+        return self._ema, m
+
+
+class TableSGD(_TableOptimizer):
+    """FlatSGD with per-group ``lr_scale`` and ``weight_decay`` in one launch (cstp_tab_sgd_step); ``momentum`` is the first
+    group's.  Same parameter lists, same checkpoint wire format (``lr_scale`` rides along in the groups, as ``eta`` does for
+    LARS); with every scale 1, one decay and no EMA a step leaves FlatSGD's bits."""
+
+    def __init__(self, params, lr, momentum=0.0, weight_decay=0.0, arenas=None):
+        params = list(params)
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=0, weight_decay=weight_decay, nesterov=False,
+                                      maximize=False, foreach=None, differentiable=False, fused=None), arenas)
+        self._buf = torch.zeros_like(self._p)
+        self._steps = 0
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        chunks, hyper = self._step_tables()
+        lr = self._lr_scalar()
+        momentum = self.param_groups[0]["momentum"]
+        if any(g["momentum"] != momentum for g in self.param_groups):
+            raise ValueError("TableSGD: one momentum for all groups (the table carries lr scale and weight decay)")
+        ema, m = self._ema_args()
+        ops.tab_sgd_step_(self._p, self._g, self._buf, chunks, hyper, lr, momentum, self._coef if self._clip_pending else None,
+                          self._steps == 0, True, ema, m)
+        self._clip_pending = False
+        self._steps += 1
+
+    # checkpoint wire format of torch.optim.SGD, as FlatSGD writes it
+    def state_dict(self):
+        sd = super().state_dict()
+        sd["state"] = _sgd_state(self)
+        return sd
+
+    def load_state_dict(self, sd):
+        _load_sgd_state(self, sd, ("lr", "momentum", "weight_decay", "lr_scale"))
+
+
+class TableAdam(_TableOptimizer):
+    """FlatAdam (``decoupled=True``: AdamW) with per-group ``lr_scale`` and ``weight_decay`` in one launch (cstp_tab_adam_step);
+    betas and eps are the first group's.  A pending clip coefficient is applied by FlatAdam's pre-pass."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False, arenas=None):
+        params = list(params)
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False,
+                                      maximize=False, foreach=None, capturable=False, differentiable=False, fused=None,
+                                      decoupled_weight_decay=bool(decoupled)), arenas)
+        self.decoupled = bool(decoupled)
+        self._m = torch.zeros_like(self._p)
+        self._v = torch.zeros_like(self._p)
+        self._steps = 0
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        chunks, hyper = self._step_tables()
+        lr = self._lr_scalar()
+        g0 = self.param_groups[0]
+        if any(tuple(g["betas"]) != tuple(g0["betas"]) or g["eps"] != g0["eps"] for g in self.param_groups):
+            raise ValueError("TableAdam: one (betas, eps) for all groups (the table carries lr scale and weight decay)")
+        if self._clip_pending:
+            self._g.mul_(self._coef)
+            self._clip_pending = False
+        self._steps += 1
+        ema, m = self._ema_args()
+        ops.tab_adam_step_(self._p, self._g, self._m, self._v, chunks, hyper, lr, g0["betas"][0], g0["betas"][1], g0["eps"],
+                           self.decoupled, self._steps, ema, m)
+
+    # checkpoint wire format of torch.optim.Adam / AdamW, as FlatAdam writes it
+    def state_dict(self):
+        sd = super().state_dict()
+        sd["state"] = _adam_state(self)
+        return sd
+
+    def load_state_dict(self, sd):
+        _load_adam_state(self, sd, ("lr", "betas", "eps", "weight_decay", "lr_scale"))
 
 
 def build_optimizer(opts, parameters, arenas):

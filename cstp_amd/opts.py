@@ -40,6 +40,21 @@ Additions (all optional, defaults reproduce the reference):
                      (cstp_amd/randaug.py, csrc/randaug.h: one operation table per layer for the whole batch; --dataset
                      synthetic_video | UcfFineTune with --transform_mode img only, refused otherwise; validation and test clips
                      are never augmented; every driver but main_ft_mp.py ignores all four)
+  --layer_decay      fine-tuning: layer-wise learning-rate decay D in (0, 1] (default 1 = off): a tensor of layer l of L trains at
+                     lr * D ** (L - l) -- the stem is layer 0, residual block b is layer b, the classifier head is layer L;
+                     r21d_byol / r3d_byol with --task ft_all | scratch | resume, refused for s3d_byol, i3d_byol and ft_fc
+  --wd_skip_1d       fine-tuning: 1 = no weight decay on tensors with dim() <= 1 (biases, BatchNorm gamma / beta) (default 0)
+  --model_ema        fine-tuning: momentum M in [0, 1) of an exponential moving average of the weights and BatchNorm statistics
+                     (default 0 = off), m = min(M, (1 + t) / (10 + t)) at update t; validation, the plateau metric and the best
+                     checkpoint then use the EMA weights, and the checkpoint gains ``state_dict_ema``; every backbone and task
+  --lr_schedule      fine-tuning: plateau (default: ReduceLROnPlateau per epoch) | cosine (linear warm-up over --warmup_epochs, then
+                     a half cosine to --min_lr, stepped per iteration)
+  --warmup_epochs    epochs of linear warm-up of --lr_schedule cosine, >= 0 and fewer than --n_epochs (default 0)
+  --min_lr           the rate --lr_schedule cosine ends at, >= 0 (default 0)
+  --test_ema         test.py: 1 = test the checkpoint's ``state_dict_ema`` (default 0: ``state_dict``)
+                     (cstp_amd/recipe.py, csrc/optim_table.h: one optimiser launch per step whatever the grouping, the EMA in the
+                     same pass; --optimizer lars takes --model_ema and refuses --layer_decay / --wd_skip_1d; every driver but
+                     main_ft_mp.py and test.py ignores all seven)
   --knn_k           weighted k-NN classification (knn.py, the --knn_every monitor): neighbours per query, 1..64 (default 20)
   --knn_t           its temperature: neighbour j weighs exp((sim_j - sim_0) / T), must be > 0 (default 0.07)
   --knn_every       main_byol.py: after every E-th epoch and after the last, rank 0 classifies the labelled test videos by k-NN
@@ -157,6 +172,13 @@ _FLAGS = [
     ("randaug_m", 9.0, float, "main_ft_mp.py: RandAugment magnitude, in [0, 30]"),
     ("randaug_mstd", 0.0, float, "main_ft_mp.py: standard deviation of the per-operation magnitude gauss(m, mstd) clipped to [0, 30], >= 0"),
     ("random_erase", 0.0, float, "main_ft_mp.py: probability in [0, 1] that a training clip gets a box erased to noise (0 = off)"),
+    ("layer_decay", 1.0, float, "main_ft_mp.py: layer-wise learning-rate decay in (0, 1] for r21d_byol / r3d_byol (1 = off)"),
+    ("wd_skip_1d", 0, int, "main_ft_mp.py: 1 = no weight decay on biases and BatchNorm parameters (tensors with dim() <= 1)"),
+    ("model_ema", 0.0, float, "main_ft_mp.py: momentum in [0, 1) of the weight EMA that is validated and checkpointed (0 = off)"),
+    ("lr_schedule", "plateau", str, "main_ft_mp.py: plateau (ReduceLROnPlateau per epoch) | cosine (warm-up + cosine per iteration)"),
+    ("warmup_epochs", 0, int, "main_ft_mp.py: warm-up epochs of --lr_schedule cosine, >= 0 and fewer than --n_epochs"),
+    ("min_lr", 0.0, float, "main_ft_mp.py: final learning rate of --lr_schedule cosine, >= 0"),
+    ("test_ema", 0, int, "test.py: 1 = load the checkpoint's state_dict_ema (written under --model_ema)"),
     ("knn_every", 0, int, "main_byol.py: k-NN top-1 of the online encoder after every E-th epoch and after the last (0 = off)"),
 ]
 RETRIEVAL_MAX_K = 64      # ops.SIM_TOPK_MAX_K: one lane per list slot

@@ -549,6 +549,28 @@ int cstp_lars_step(void* stream, float* p, float* g, float* buf, size_t n, const
                    const int32_t* segs, int32_t n_segs, const float* ratio, const float* lr, float momentum, float weight_decay,
                    const float* coef, int32_t write_back_grad);
 
+/* cstp_sgd_step / cstp_adam_step with PER-TENSOR hyper-parameters (layer-wise learning-rate decay, no weight decay on biases and
+ * BatchNorm vectors) and an optional weight EMA in the same pass: ONE launch whatever the grouping.  The trainable tensors are
+ * described by the chunk table of LARS above (chunks [n_chunks][3] = {segment, offset, length}; frozen tensors are not listed and
+ * are never touched) and a DEVICE float table
+ *   hyper [n_segs][2] = {lr scale, weight decay}: one tensor
+ * over arenas of n floats (n < 2^31).  With s the chunk's segment, scale = hyper[s][0], wd = hyper[s][1], and lr[0] * scale ONE
+ * fp32 product (lr is the DEVICE scalar of the plain entry points):
+ *   cstp_tab_sgd_step:   g' = g*coef[0] (coef may be NULL); if write_back_grad: g = g';  g' += wd*p;
+ *                        buf = first_step ? g' : momentum*buf + g';  p -= (lr[0]*scale)*buf
+ *   cstp_tab_adam_step:  with l = lr[0]*scale: decoupled = 0: g += wd*p / decoupled = 1: p *= 1 - l*wd;
+ *                        m = b1*m + (1-b1)*g; v = b2*v + (1-b2)*g*g;  p -= l/(1-b1^step) * m / (sqrt(v)/sqrt(1-b2^step) + eps)
+ * the fp32 expressions of cstp_sgd_step / cstp_adam_step: with every scale 1 and one wd the results are theirs bit for bit.
+ * ema (may be NULL; an arena of the layout of p): after the update, ema = ema_momentum*ema + (1 - ema_momentum)*p, the expression
+ * of cstp_ema_update, saving that pass's read of p and its launch.  One block per chunk, no atomics, no host read: equal inputs
+ * give equal bits; zero padding stays zero in every arena; a table entry that points outside the arena or the tables is skipped. */
+int cstp_tab_sgd_step(void* stream, float* p, float* g, float* buf, float* ema, size_t n, const int32_t* chunks, int32_t n_chunks,
+                      const float* hyper, int32_t n_segs, const float* lr, float momentum, const float* coef, int32_t first_step,
+                      int32_t write_back_grad, float ema_momentum);
+int cstp_tab_adam_step(void* stream, float* p, const float* g, float* exp_avg, float* exp_avg_sq, float* ema, size_t n,
+                       const int32_t* chunks, int32_t n_chunks, const float* hyper, int32_t n_segs, const float* lr, float beta1,
+                       float beta2, float eps, int32_t decoupled, int32_t step, float ema_momentum);
+
 /* ---- the bf16-STORAGE path (BASELINE configs[4]: 3D-ResNet-50 backbone swap, bf16) --------------------------------
  * The ATen call-sites of models/BE/r3d_byol.py under bf16 activations (what torch.autocast(bfloat16) makes of them): every
  * 5-D activation tensor and every gradient of one is bf16 in HBM (uint16_t* below = raw bf16 bits, NCDHW, contiguous), all

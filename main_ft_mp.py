@@ -30,10 +30,16 @@ cstp_soft_cross_entropy_*); training accuracy is then taken against the target t
 cstp_droppath_add_relu_*), in training forwards only.  --randaug_n / --randaug_m / --randaug_mstd and --random_erase augment the
 TRAINING clips of --dataset synthetic_video | UcfFineTune under --transform_mode img with RandAugment and random erasing on the
 8-bit frames of the whole batch (cstp_amd.randaug, cstp_randaug_layer / cstp_randaug_finish); validation clips never are.
+--layer_decay, --wd_skip_1d, --model_ema, --lr_schedule cosine (--warmup_epochs, --min_lr) are the optimisation half of that recipe
+(cstp_amd.recipe): per-tensor learning-rate scales and weight decays in ONE optimiser launch (optim.TableSGD / TableAdam,
+cstp_tab_sgd_step / cstp_tab_adam_step), a weight EMA updated in that same launch -- validation, the plateau metric and the best
+checkpoint then use the EMA weights, and the checkpoint gains ``state_dict_ema`` beside the unchanged ``state_dict`` -- and a
+warm-up + cosine schedule stepped per iteration in place of the plateau scheduler.
 """
 from __future__ import annotations
 
 import builtins
+import contextlib
 import os
 import random
 import time
@@ -42,14 +48,12 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from cstp_amd import ops, randaug
+from cstp_amd import ops, randaug, recipe
 from cstp_amd.mix import build_mixer
 from cstp_amd.model import generate_model
-from cstp_amd.optim import build_optimizer
 from cstp_amd.regularize import build_regularizer
 from cstp_amd.opts import parse_opts
 from cstp_amd.device_batches import DeviceBatches
-from cstp_amd.scheduler import ReduceLROnPlateau
 from cstp_amd.synthetic import SyntheticLabelledClips
 from cstp_amd.train import FineTuneStep, sync_buffers
 from cstp_amd.utils import AverageMeter, Logger, calculate_accuracy, get_dataloader
@@ -111,7 +115,8 @@ def o_type_for(task):
     return "ft_all" if task in ("scratch", "resume") else task
 
 
-def train(epoch, train_dataloader, step_fn, optimizer, opts, train_logger, len_train_data):
+def train(epoch, train_dataloader, step_fn, optimizer, opts, train_logger, len_train_data, schedule=None):
+    """``schedule``: the per-iteration recipe.WarmupCosine of --lr_schedule cosine (None: the rate changes per epoch at most)."""
     step_fn.model.train()
     batch_time, data_time, losses, accuracies = AverageMeter(), AverageMeter(), AverageMeter(), AverageMeter()
     end_time = time.time()
@@ -120,6 +125,8 @@ def train(epoch, train_dataloader, step_fn, optimizer, opts, train_logger, len_t
     for inputs, targets in DeviceBatches(train_dataloader, opts.device):
         i += 1
         data_time.update(time.time() - end_time)
+        if schedule is not None:
+            schedule.step()
         loss, outputs = step_fn(inputs, targets)
         acc = calculate_accuracy(outputs, step_fn.accuracy_targets(targets))   # under mixing: the heavier target
         reduced_loss = reduce_mean(loss, opts.world_size)
@@ -144,7 +151,10 @@ def train(epoch, train_dataloader, step_fn, optimizer, opts, train_logger, len_t
     return losses.avg, accuracies.avg
 
 
-def validation(epoch, val_dataloader, model, optimizer, opts, val_logger, len_val_data, scheduler):
+def validation(epoch, val_dataloader, model, optimizer, opts, val_logger, len_val_data, scheduler, ema=False):
+    """``scheduler``: the plateau scheduler, or None under --lr_schedule cosine.  ``ema`` (--model_ema): the loop below runs on the EMA
+    weights and EMA BatchNorm statistics, so the plateau metric and the best-checkpoint choice are theirs; the checkpoint keeps the
+    raw weights under ``state_dict`` and gains ``state_dict_ema`` with the same keys."""
     batch_time, data_time, losses, accuracies = AverageMeter(), AverageMeter(), AverageMeter(), AverageMeter()
     o_type = o_type_for(opts.task)
     n_iter = int(len_val_data / opts.batch_size)
@@ -152,7 +162,10 @@ def validation(epoch, val_dataloader, model, optimizer, opts, val_logger, len_va
     # DDP(broadcast_buffers=True) hands rank 0's running statistics to every rank at the first eval forward too
     # (models/model.py:97-103): every rank validates -- and rank 0 checkpoints -- the same statistics
     sync_buffers(model)
-    with torch.no_grad():
+    state_dict_ema = None
+    with (recipe.ema_applied(model.module, optimizer) if ema else contextlib.nullcontext()), torch.no_grad():
+        if ema and opts.rank == 0 and opts.local_rank == 0:
+            state_dict_ema = {k: v.clone() for k, v in model.state_dict().items()}
         i = 0
         for inputs, targets in DeviceBatches(val_dataloader, opts.device):
             end_time = time.time()
@@ -175,7 +188,8 @@ def validation(epoch, val_dataloader, model, optimizer, opts, val_logger, len_va
         t = torch.tensor([losses.sum, float(losses.count)], dtype=torch.float64, device=torch.device("cuda", opts.device))
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         val_loss = float(t[0] / t[1].clamp(min=1))
-    scheduler.step(val_loss)
+    if scheduler is not None:
+        scheduler.step(val_loss)
     if opts.rank == 0 and opts.local_rank == 0:
         val_logger.log({"epoch": epoch, "loss": losses.avg, "acc": accuracies.avg})
         accuracy_val = accuracies.avg
@@ -187,8 +201,10 @@ def validation(epoch, val_dataloader, model, optimizer, opts, val_logger, len_va
             opts.highest_val.pop(old_key)
             opts.highest_val["save_{}_max.pth".format(epoch)] = accuracy_val
             save_file_path = os.path.join(opts.result_path, opts.dataset, opts.task, "save_{}_max.pth".format(epoch))
-            torch.save({"epoch": epoch + 1, "arch": opts.arch, "state_dict": model.state_dict(),
-                        "optimizer": optimizer.state_dict()}, save_file_path)
+            checkpoint = {"epoch": epoch + 1, "arch": opts.arch, "state_dict": model.state_dict(), "optimizer": optimizer.state_dict()}
+            if ema:
+                checkpoint["state_dict_ema"] = state_dict_ema
+            torch.save(checkpoint, save_file_path)
     return val_loss, accuracies.avg
 
 
@@ -210,6 +226,7 @@ def main_worker(local_rank, opts):
         raise ValueError("main_ft_mp.py serves --task %s, got %r" % ("/".join(TRAIN_TASKS), opts.task))
     regularizer = build_regularizer(opts)        # --dropout / --drop_path: refused here, before any data or model is built
     augment = randaug.from_opts(opts)            # --randaug_* / --random_erase likewise; None at the defaults
+    plan = recipe.check_flags(opts)              # --layer_decay / --wd_skip_1d / --model_ema / --lr_schedule ... likewise
 
     print("Preprocessing train data ...")
     train_data = build_dataset(opts, "train", augment)
@@ -238,10 +255,23 @@ def main_worker(local_rank, opts):
                                                                opts.model_depth)),
                             ["epoch", "loss", "acc"], overlay=not resume)
 
-    optimizer = build_optimizer(opts, parameters, inner.flatten_parameters())
+    # at the defaults: optim.build_optimizer's FlatSGD / FlatAdam / FlatLARS and the plateau scheduler, as before these flags
+    optimizer = recipe.build_optimizer(opts, inner, parameters, inner.flatten_parameters())
+    print("Optimizer:", type(optimizer).__name__)
+    resume_md = torch.load(opts.resume_md_path, map_location=torch.device("cuda", local_rank)) if resume else None
     if resume:
-        optimizer.load_state_dict(torch.load(opts.resume_md_path, map_location=torch.device("cuda", local_rank))["optimizer"])
-    scheduler = ReduceLROnPlateau(optimizer, "min", patience=opts.lr_patience)
+        optimizer.load_state_dict(resume_md["optimizer"])
+    ema = plan.model_ema > 0.0
+    if ema:                                      # the shadows start from the loaded weights ...
+        optimizer.enable_ema(plan.model_ema)
+        if resume and "state_dict_ema" in resume_md:         # ... or continue the checkpoint's
+            recipe.load_ema_state_dict(model, inner, optimizer, resume_md["state_dict_ema"])
+    resume_md = None
+    iters_per_epoch = len(train_dataloader)
+    if opts.max_steps:
+        iters_per_epoch = min(iters_per_epoch, opts.max_steps)
+    scheduler = recipe.build_scheduler(opts, optimizer, iters_per_epoch, begin_epoch)
+    cosine = plan.lr_schedule == "cosine"        # stepped per iteration in train(); the plateau scheduler is then not built
     # --label_smoothing / --mixup_alpha / --cutmix_alpha (all tasks served here); None at the defaults.  Training only:
     # validation below keeps the plain cross-entropy, so the plateau scheduler's metric stays comparable between runs
     # --dropout / --drop_path likewise: None at the defaults, training forwards only
@@ -253,9 +283,9 @@ def main_worker(local_rank, opts):
         if train_sampler is not None:
             train_sampler.set_epoch(epoch)
         step_fn.set_epoch(epoch)
-        train(epoch, train_dataloader, step_fn, optimizer, opts, train_logger, len_train_data)
+        train(epoch, train_dataloader, step_fn, optimizer, opts, train_logger, len_train_data, scheduler if cosine else None)
         print("Start validating epoch {}".format(epoch))
-        validation(epoch, val_dataloader, model, optimizer, opts, val_logger, len_val_data, scheduler)
+        validation(epoch, val_dataloader, model, optimizer, opts, val_logger, len_val_data, None if cosine else scheduler, ema)
     if opts.distributed:
         dist.barrier()
         dist.destroy_process_group()

@@ -12,6 +12,7 @@ clip logits averaged per video, top-5 from the mean, running top-1 accuracy, one
 New: --dataset synthetic_video --transform_mode img_test plans every clip of a video as UcfFineTune._get_test_clip does
 (datasets.py:1062-1097) and assembles them on the device in two launches (cstp_amd.clip_ops.assemble_batch); it also prints the
 clip count of each video; --dataset UcfFineTune does the same from UCF-style frame folders (cstp_amd.frame_folder).
+--test_ema 1 tests the checkpoint's ``state_dict_ema`` (the EMA weights main_ft_mp.py --model_ema writes) instead of ``state_dict``.
 """
 from __future__ import annotations
 
@@ -59,6 +60,8 @@ def run(opts):
     opts.device = torch.device("cuda:0")
     print(opts)
     opts.arch = "{}-{}".format(opts.model_name, opts.model_depth)
+    if getattr(opts, "test_ema", 0) not in (0, 1):          # refused here, before any data or model is built
+        raise ValueError("--test_ema is 0 or 1, got %r" % (opts.test_ema,))
     print("Preprocessing testing data ...")
     test_data = build_dataset(opts)
     print("Length of testing data = ", len(test_data))
