@@ -536,7 +536,9 @@ igemm_k1s(const Geom g, const uint4* __restrict__ wps, const float* __restrict__
       const unsigned sb = have ? (unsigned)(cg << 4) * ch4 : 0u;    // scalar part: first channel of the block
 #pragma unroll
       for (int h = 0; h < NH; ++h) {
-        const unsigned vo = have ? vb0[h] : OOB;      // the range check looks at the vector offset only
+        // gfx950 range-checks vector + scalar offset together: the padded channels of the LAST sample,
+        // whose scalar part points past the tensor, load 0 like any OOB offset; OOB + sb stays below 2^32, so it never wraps
+        const unsigned vo = have ? vb0[h] : OOB;
 #pragma unroll
         for (int j = 0; j < 16; ++j) buf_load_x1(rb[h][j], vo, rs_src, sb + ch4 * (unsigned)j);
       }

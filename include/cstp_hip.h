@@ -581,8 +581,9 @@ int cstp_tab_adam_step(void* stream, float* p, const float* g, float* exp_avg, f
  * multiples of 16, such as R(2+1)D's mid channels 83 / 230 / 460 / 921, are gathered in 16-channel groups whose last one is
  * partial: the missing channels read as zero and meet zero-padded packed weights; no padded copy of the activation) -- or, above
  * 27 taps, any channel count with taps * channels <= 1056 (the 3-channel 7x7x7 / 1x7x7 stems through a zero-padded copy and an
- * offset table, forward and weight gradient only); every gathered tensor < 2 GiB.  Anything else is refused with an error, not
- * emulated. */
+ * offset table, forward and weight gradient only); every gathered tensor < 2 GiB; the bf16 OUTPUT of the forward and of the data
+ * gradient 8-byte aligned (four values per store; refused before anything is launched; the gathered operands may start at
+ * any element).  Anything else is refused with an error, not emulated. */
 /* x.to(torch.bfloat16) of the clip (r3d_byol.py:193-194 under autocast): n floats -> n bf16, round to nearest even. */
 int cstp_b16_cast(void* stream, const float* x, uint16_t* y, size_t n);
 size_t cstp_b16_conv3d_workspace_bytes(const cstp_conv_desc* desc);
