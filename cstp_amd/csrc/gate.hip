@@ -53,6 +53,11 @@ __global__ void __launch_bounds__(256) gate_mean_kernel(GateSet gs, int rows, in
       const float4 v = x4[j];
       acc += (v.x + v.y) + (v.z + v.w);
     }
+  } else if ((s & 3) == 0) {      // rows off a 16-byte boundary: the float4 body's order of additions, so the bits do not depend on alignment
+    for (int j = lane; j < (s >> 2); j += 64) {
+      const float* v = x + 4 * j;
+      acc += (v[0] + v[1]) + (v[2] + v[3]);
+    }
   } else {
     for (int j = lane; j < s; j += 64) acc += x[j];
   }
@@ -132,6 +137,15 @@ __global__ void __launch_bounds__(256) gate_dot_kernel(GateSet gs, int rows, int
       t = __builtin_fmaf(a.y, b.y, t);
       t = __builtin_fmaf(a.z, b.z, t);
       t = __builtin_fmaf(a.w, b.w, t);
+    }
+  } else if ((s & 3) == 0) {      // ... and here the float4 body's chain of four per lane
+    for (int j = lane; j < (s >> 2); j += 64) {
+      const float* a = x + 4 * j;
+      const float* b = dyr + 4 * j;
+      t = __builtin_fmaf(a[0], b[0], t);
+      t = __builtin_fmaf(a[1], b[1], t);
+      t = __builtin_fmaf(a[2], b[2], t);
+      t = __builtin_fmaf(a[3], b[3], t);
     }
   } else {
     for (int j = lane; j < s; j += 64) t = __builtin_fmaf(x[j], dyr[j], t);

@@ -633,7 +633,8 @@ int cstp_b16_avgpool_backward(void* stream, const float* dy, uint16_t* dx, int32
  * and the torch.cat((x0, x1, x2, x3), 1) that follows them.  Branch i: x_i [n][c_i][s] (the output of its last BN+ReLU),
  * w_i [c_i][c_i], b_i [c_i]; it occupies channels [o_i, o_i + c_i) of y [n][C][s], C = sum c_i, o_i = c_0 + .. + c_{i-1}.
  * m [n][C] receives the means, g [n][C] the gates.  Reductions run in a fixed order and no float atomics are used: two calls
- * with the same inputs give bit-identical outputs. */
+ * with the same inputs give bit-identical outputs, whether or not the pointers are 16-byte aligned (the scalar bodies that
+ * serve unaligned rows with s % 4 == 0 add in the order of the 16-byte ones). */
 typedef struct cstp_gate_branch {
   const float* x;      /* [n][c][s] branch output */
   const float* w;      /* [c][c] gating Linear weight (fc.weight) */

@@ -13,12 +13,30 @@ outputs, its workspace and the fp64 checks of its results -- and ``three_runs`` 
 Inputs take the run's fill in both guards (``nan`` = 0xFF bytes: NaN as fp32 and as bf16, -1 as int32).  Outputs always have
 0xFF guards and a 0xFF interior, so an element the call never wrote reads as NaN; an output with a ``prior`` (an accumulating
 call, running statistics) starts from those finite values instead.  The workspace is 0xFF inside and out: its content on entry
-is unspecified.  Device-agnostic: the host test drives the same code with plain torch implementations on the CPU."""
+is unspecified.  Device-agnostic: the host test drives the same code with plain torch implementations on the CPU.
+
+In-place operands ("What an in-place call may touch").  An operand that a call reads AND writes -- p, g, buf, the
+moments, ema, running statistics, a ring, an accumulate target -- is an output with a ``prior``.  Its check is usually two checks
+(``all_checks``): the numeric one on the elements the call owns, and ``untouched_check(prior, mask)`` on the rest, which asserts
+BIT equality with the prior wherever ``mask`` is set and names the first changed element.
+
+Several tensors inside one operand.  A case may carve slices out of one guarded arena -- the tensors of a parameter arena, or
+dw | db | dgamma | dbeta of a gradient arena -- by handing the call ``view.data_ptr() + 4 * offset``.  What lies between the
+slices (padding, a frozen tensor, another layer's live gradient) is part of the prior and goes into the mask of
+``untouched_check``; no class of its own is needed.
+
+A call may be a pair.  Where a workspace carries state from a forward to its backward (cstp_ntxent_*, cstp_ntxq_*), ``impl``
+makes both calls: the workspace is poisoned before the forward only, and the backward must find there what the forward wrote.
+
+What poison cannot show.  A read-modify-write of a guard leaves 0xFF (and 0x00) bytes unchanged: NaN in, NaN out.  Cases with
+in-place operands therefore make a fourth run, ``live_run``, in which the guards of those operands hold a finite non-zero
+pattern, as a live neighbour in an arena would."""
 import torch
 
 MIN_GUARD = 64 * 1024
 PAGE = 4096
 FILLS = {"zero": 0x00, "nan": 0xFF}
+LIVE = 0x3C                  # 0x3C3C3C3C is 0.0115 as fp32, 0x3C3C 0.0115 as bf16: a finite, non-zero neighbour
 
 
 def guard_bytes(nbytes):
@@ -122,14 +140,15 @@ class Operands:
         self.outs = {n: Guarded(s, d, device, spec.shifts.get(n, 0), n) for n, (s, d) in spec.outputs.items()}
         self.ws = Guarded((max(spec.ws_bytes, 1),), torch.uint8, device, 0, "the workspace")
 
-    def arm(self, fill):
+    def arm(self, fill, live=False):
+        """live: the guards of every output with a prior hold LIVE bytes (a finite neighbour) instead of 0xFF (live_run)."""
         byte = FILLS[fill]
         for n, g in self.ins.items():
             g.set_guards(byte)
             g.load(self.spec.inputs[n])
             g.remember()
         for n, g in self.outs.items():
-            g.set_guards(0xFF)
+            g.set_guards(LIVE if live and n in self.spec.priors else 0xFF)
             if n in self.spec.priors:
                 g.load(self.spec.priors[n])
             else:
@@ -171,9 +190,9 @@ def _finite_problem(spec, name, got):
     return None
 
 
-def one_run(spec, ops, impl, fill, sync=None):
+def one_run(spec, ops, impl, fill, sync=None, live=False):
     """Arm, call, and hold the run to assertions 1-3.  Returns ({output: CPU copy}, [problems])."""
-    ops.arm(fill)
+    ops.arm(fill, live)
     impl(ops.views())
     if sync is not None:
         sync()
@@ -225,9 +244,79 @@ def single_run(spec, impl, device, sync=None, fill="nan"):
     return one_run(spec, Operands(spec, device), impl, fill, sync)[1]
 
 
+def live_run(spec, impl, device, sync=None):
+    """One more run, for calls that update operands IN PLACE: assertions 1-3 with LIVE bytes in the guards of every output that
+    has a prior.  An in-place update of poison is poison -- 0.37 * NaN is the same NaN, and m * 0 + (1 - m) * 0 the same 0 -- so a
+    read-modify-write one element too wide, or of a table entry that should have been skipped, leaves 0xFF and 0x00 guards as it
+    found them; a finite non-zero neighbour changes.  (The three runs stay: only they see a guard READ into a result.)"""
+    return one_run(spec, Operands(spec, device), impl, "nan", sync, live=True)[1]
+
+
 def rel_check(ref64, tol):
     """max |got - ref| / max |ref| < tol (conftest.rel_err, the metric of every parity test here)."""
     def check(got):
         err = float((got.double() - ref64).abs().max() / ref64.abs().max().clamp_min(1e-30))
         assert err < tol, "relative error %.3e (bar %.1e)" % (err, tol)
+    return check
+
+
+def ulp_bf16(ref):
+    """One bf16 unit in the last place at |ref| (fp64)."""
+    e = torch.floor(torch.log2(ref.abs().clamp_min(2.0 ** -126)))
+    return torch.pow(torch.tensor(2.0, dtype=torch.float64), e - 7)
+
+
+def rounded_check(exact64):
+    """test_b16_gpu.py's check_rounded: within one bf16 ulp everywhere, fewer than 1e-3 of the elements off the rounded value."""
+    def check(got_b16):
+        got, want = got_b16.double(), exact64.to(torch.bfloat16).double()
+        err = (got - exact64).abs()
+        bad = err > ulp_bf16(exact64) + 1e-5 * float(exact64.abs().max())
+        assert not bool(bad.any()), "%d elements further than one bf16 ulp, worst %g" % (int(bad.sum()), float(err.max()))
+        flips = float((got != want).double().mean())
+        assert flips < 1e-3, "%.2e of the elements differ from the correctly rounded value" % flips
+    return check
+
+
+def bits_check(ref, mask=None):
+    """Bit equality with ``ref`` (same dtype) -- everywhere, or where ``mask`` is set -- reporting the first differing element."""
+    def check(got):
+        assert got.dtype == ref.dtype and got.numel() == ref.numel(), (got.dtype, ref.dtype, tuple(got.shape), tuple(ref.shape))
+        item = got.element_size()
+        differ = (got.contiguous().view(torch.uint8).view(-1, item) != ref.contiguous().view(torch.uint8).view(-1, item)).any(dim=1)
+        if mask is not None:
+            differ &= mask.flatten()
+        diff = differ.nonzero()
+        if diff.numel():
+            first = int(diff[0])
+            raise AssertionError("%s differ in their bits (first: element %d; expected %r, got %r)" % (
+                _plural(int(diff.numel()), "element"), first, ref.flatten()[first].item(), got.flatten()[first].item()))
+    return check
+
+
+def untouched_check(prior, mask):
+    """The elements of an in-place operand that the call must leave alone: wherever ``mask`` (bool, the operand's shape) is set,
+    the result is the ``prior`` bit for bit.  Reports how many changed and the first one, as a flat element index."""
+    prior, mask = prior.contiguous(), mask.contiguous().flatten()
+    assert mask.dtype == torch.bool and mask.numel() == prior.numel()
+
+    def check(got):
+        assert got.dtype == prior.dtype and got.numel() == prior.numel(), (got.dtype, prior.dtype)
+        item = got.element_size()
+        a = got.contiguous().view(torch.uint8).view(-1, item)
+        b = prior.view(torch.uint8).view(-1, item)
+        changed = ((a != b).any(dim=1) & mask).nonzero()
+        if changed.numel():
+            first = int(changed[0])
+            raise AssertionError("changed %s that the call must leave untouched (first: element %d of %d; was %r, is %r)" % (
+                _plural(int(changed.numel()), "element"), first, prior.numel(), prior.flatten()[first].item(),
+                got.flatten()[first].item()))
+    return check
+
+
+def all_checks(*checks):
+    """One check out of several (the numeric check of the elements a call owns, then untouched_check of the rest)."""
+    def check(got):
+        for c in checks:
+            c(got)
     return check

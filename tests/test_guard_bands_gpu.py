@@ -522,21 +522,7 @@ B16_CONVS = {
 }
 
 
-def ulp_bf16(ref):
-    e = torch.floor(torch.log2(ref.abs().clamp_min(2.0 ** -126)))
-    return torch.pow(torch.tensor(2.0, dtype=F64), e - 7)
-
-
-def rounded_check(exact64):
-    """test_b16_gpu.py's check_rounded: within one bf16 ulp everywhere, fewer than 1e-3 of the elements off the rounded value."""
-    def check(got_b16):
-        got, want = got_b16.double(), exact64.to(B16).double()
-        err = (got - exact64).abs()
-        bad = err > ulp_bf16(exact64) + 1e-5 * float(exact64.abs().max())
-        assert not bool(bad.any()), "%d elements further than one bf16 ulp, worst %g" % (int(bad.sum()), float(err.max()))
-        flips = float((got != want).double().mean())
-        assert flips < 1e-3, "%.2e of the elements differ from the correctly rounded value" % flips
-    return check
+ulp_bf16, rounded_check = gb.ulp_bf16, gb.rounded_check      # (shared with tests/test_guard_bands_ops_gpu.py)
 
 
 @functools.lru_cache(maxsize=None)
