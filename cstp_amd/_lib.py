@@ -211,6 +211,12 @@ SIGNATURES = {
     "cstp_probe_step": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P,
                                   c_size_t]),
     "cstp_probe_predict": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P]),
+    # the same for up to 32 classifiers side by side: head = grid dimension (csrc/probe.h)
+    "cstp_probe_sweep_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "cstp_probe_sweep_step": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P,
+                                        _P, _P, _P, c_size_t]),
+    "cstp_probe_sweep_score": (c_int32, [_P, _P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P,
+                                         _P, c_size_t]),
     # NT-Xent with a queue of extra negatives (csrc/ntxq.h)
     "cstp_ntxq_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "cstp_ntxq_forward": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_float, _P, c_size_t]),

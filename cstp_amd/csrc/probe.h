@@ -3,11 +3,12 @@
 //
 // The operand that streams is the activation matrix (1 000 - 10 000 rows), the classes are few (<= 1024) and the arithmetic
 // (2 m d c FLOP) is small next to the launches and the traffic, so both products are plain fp32 FMA tiles through LDS:
-//   1. probe_logits_kernel<STEP>  block = 256 threads owns PR_TM = 8 rows.  Per tile of PR_CT = 128 classes it walks d in chunks
+//   1. probe_logits_kernel<MODE>  block = 256 threads owns PR_TM = 8 rows.  Per tile of PR_CT = 128 classes it walks d in chunks
 //      of PR_BK = 32 (global -> registers -> LDS, the next chunk in flight while the current one is multiplied); lane = class,
 //      wave = row pair, one fmaf chain per (row, class) in feature order.  The slab's logits stay in LDS ([8][c] floats); a wave
 //      then owns two rows: arg-max (lowest class id first), soft-max about the row maximum, and
 //        STEP:    g = (p - onehot) / m as [m][cpad] into the workspace (cpad = c rounded up to 4, padding zero), row loss, row hit
+//        score:   row loss and row hit only
 //        predict: n_top rounds of a wave-wide arg-max over what comes after the previous pick in (logit desc, class asc)
 //   2. probe_wgrad_kernel   block owns a 64 class x 64 feature tile of dw and one slice of the rows; 16 rows of g and of the
 //      standardised x per LDS chunk, thread = 4 x 4 outputs, one fmaf chain per output over the slice's rows ascending.  The
@@ -16,6 +17,14 @@
 //      its last block folds db the same way and sums row loss (in double) and row hits in one fixed tree.
 // Every sum has one writer and one order: no atomics, equal inputs give equal bits.  A gathered index outside [0, n) or a label
 // outside [0, c) is compared, never used to form an address: the row's x is taken as zeros and its g, loss and hit are zero.
+//
+// Sweep (cstp_probe_sweep_step / cstp_probe_sweep_score): `heads` classifiers on the same batch in the same launches.  Head h
+// reads (w, b) + h * head_stride floats, writes (dw, db) at the same stride and owns workspace bytes [h * round16(single),
+// (h + 1) * round16(single)), laid out as the single-head workspace is.  The head is blockIdx.y of launches 1 and 3 and a factor
+// of blockIdx.z of launch 2 (z = head * slices + slice); everything else -- chains, reductions, slices, fold order -- is the
+// single-head code, which the old entry points run with heads = 1, so head h has the bits of the single-head call on (W_h, b_h).
+// LDS per block is unchanged (8 c floats dynamic): heads multiply blocks, not a block's footprint.  Score mode writes row loss
+// and row hit only (no g, no launch 2) and its fold block sums them: two launches.
 #pragma once
 #include <math.h>
 
@@ -62,13 +71,25 @@ __device__ __forceinline__ int pr_source(const int32_t* __restrict__ rows, int r
 }
 
 // vec bits: 1 = x rows, 2 = w rows, 4 = mean / inv_std may be read as float4
-template <bool STEP>
+// MODE: PR_PREDICT ranks classes; PR_STEP writes g, row loss, row hit; PR_SCORE row loss and row hit only.  blockIdx.y = head:
+// w, b advance by head_stride floats, g / row_loss / row_hit by ws_stride floats (both 0 with one head)
+enum { PR_PREDICT = 0, PR_STEP = 1, PR_SCORE = 2 };
+
+template <int MODE>
 __global__ void __launch_bounds__(256)
 probe_logits_kernel(const float* __restrict__ x, const int32_t* __restrict__ rows, const int64_t* __restrict__ labels,
                     const float* __restrict__ mean, const float* __restrict__ inv_std, const float* __restrict__ w,
-                    const float* __restrict__ b, int m, int n, int d, int c, int cpad, int vec, float inv_m,
-                    float* __restrict__ g, float* __restrict__ row_loss, int* __restrict__ row_hit, int n_top,
+                    const float* __restrict__ b, size_t head_stride, size_t ws_stride, int m, int n, int d, int c, int cpad, int vec,
+                    float inv_m, float* __restrict__ g, float* __restrict__ row_loss, int* __restrict__ row_hit, int n_top,
                     int* __restrict__ pred, float* __restrict__ score) {
+  constexpr bool STEP = MODE != PR_PREDICT;
+  if (STEP && blockIdx.y != 0) {
+    w += blockIdx.y * head_stride;
+    b += blockIdx.y * head_stride;
+    if (MODE == PR_STEP) g += blockIdx.y * ws_stride;
+    row_loss += blockIdx.y * ws_stride;
+    row_hit += blockIdx.y * ws_stride;
+  }
   extern __shared__ float Ls[];                                           // [PR_TM][c] logits of the slab
   __shared__ __attribute__((aligned(16))) float Ws[PR_CT * PR_LDK];
   __shared__ __attribute__((aligned(16))) float Xs[PR_TM * PR_LDK];
@@ -163,11 +184,13 @@ probe_logits_kernel(const float* __restrict__ x, const int32_t* __restrict__ row
       const int64_t y64 = src >= 0 ? labels[src] : -1;
       const bool valid = src >= 0 && y64 >= 0 && y64 < c;
       const int y = valid ? (int)y64 : -1;
-      const float inv_sum = 1.f / sum;
-      for (int k = lane; k < cpad; k += 64) {
-        float gv = 0.f;
-        if (valid && k < c) gv = (expf(L[k] - bv) * inv_sum - (k == y ? 1.f : 0.f)) * inv_m;
-        g[(size_t)r * cpad + k] = gv;
+      if (MODE == PR_STEP) {
+        const float inv_sum = 1.f / sum;
+        for (int k = lane; k < cpad; k += 64) {
+          float gv = 0.f;
+          if (valid && k < c) gv = (expf(L[k] - bv) * inv_sum - (k == y ? 1.f : 0.f)) * inv_m;
+          g[(size_t)r * cpad + k] = gv;
+        }
       }
       if (lane == 0) {
         row_loss[r] = valid ? (logf(sum) + bv) - L[y] : 0.f;
@@ -212,15 +235,22 @@ probe_logits_kernel(const float* __restrict__ x, const int32_t* __restrict__ row
   }
 }
 
-// out: dw when gridDim.z == 1, otherwise the partials [slice][c][d]; dbp [slice][c]
+// out: dw when nslice == 1, otherwise the partials [slice][c][d]; dbp [slice][c].  blockIdx.z = head * nslice + slice: g and dbp
+// advance by ws_stride floats per head, out by out_stride (the workspace stride for partials, the head stride for dw itself)
 __global__ void __launch_bounds__(256)
 probe_wgrad_kernel(const float* __restrict__ x, const int32_t* __restrict__ rows, const float* __restrict__ mean,
                    const float* __restrict__ inv_std, const float* __restrict__ g, int m, int n, int d, int c, int cpad, int vec,
-                   int rows_per_slice, float* __restrict__ out, float* __restrict__ dbp) {
+                   int rows_per_slice, int nslice, size_t ws_stride, size_t out_stride, float* __restrict__ out,
+                   float* __restrict__ dbp) {
   __shared__ __attribute__((aligned(16))) float Gs[PR_GR * PR_GT];
   __shared__ __attribute__((aligned(16))) float Xs[PR_GR * PR_GT];
   const int tid = threadIdx.x, tc = tid & 15, td = tid >> 4;
-  const int d0 = blockIdx.x * PR_GT, c0 = blockIdx.y * PR_GT, slice = blockIdx.z;
+  const int d0 = blockIdx.x * PR_GT, c0 = blockIdx.y * PR_GT, head = blockIdx.z / nslice, slice = blockIdx.z - head * nslice;
+  if (head != 0) {
+    g += head * ws_stride;
+    dbp += head * ws_stride;
+    out += head * out_stride;
+  }
   const int r_begin = slice * rows_per_slice;
   const int r_end = r_begin + rows_per_slice < m ? r_begin + rows_per_slice : m;
   const bool vx = vec & 1, vm = vec & 4, vo = vec & 8;
@@ -282,13 +312,27 @@ probe_wgrad_kernel(const float* __restrict__ x, const int32_t* __restrict__ rows
   }
 }
 
+// blockIdx.y = head: the workspace operands advance by ws_stride floats, dw / db by head_stride, loss / hits by one.  db NULL
+// (score): the last block sums row loss and row hits only
 __global__ void __launch_bounds__(256)
 probe_fold_kernel(const float* __restrict__ partial, int nslice, size_t cd, int fold_blocks, float* __restrict__ dw,
                   const float* __restrict__ dbp, int c, float* __restrict__ db, const float* __restrict__ row_loss,
-                  const int* __restrict__ row_hit, int m, float* __restrict__ loss, int* __restrict__ hits) {
+                  const int* __restrict__ row_hit, int m, float* __restrict__ loss, int* __restrict__ hits, size_t head_stride,
+                  size_t ws_stride) {
   __shared__ double sd[16];
   __shared__ int si[16];
   const int tid = threadIdx.x;
+  if (blockIdx.y != 0) {
+    const size_t h = blockIdx.y;
+    partial += h * ws_stride;
+    dbp += h * ws_stride;
+    row_loss += h * ws_stride;
+    row_hit += h * ws_stride;
+    if (dw != nullptr) dw += h * head_stride;
+    if (db != nullptr) db += h * head_stride;
+    loss += h;
+    hits += h;
+  }
   if ((int)blockIdx.x < fold_blocks) {
     const size_t i = (size_t)blockIdx.x * 256 + tid;
     if (i < cd) {
@@ -298,10 +342,12 @@ probe_fold_kernel(const float* __restrict__ partial, int nslice, size_t cd, int 
     }
     return;
   }
-  for (int k = tid; k < c; k += 256) {
-    float s = 0.f;
-    for (int sl = 0; sl < nslice; ++sl) s += dbp[(size_t)sl * c + k];
-    db[k] = s;
+  if (db != nullptr) {
+    for (int k = tid; k < c; k += 256) {
+      float s = 0.f;
+      for (int sl = 0; sl < nslice; ++sl) s += dbp[(size_t)sl * c + k];
+      db[k] = s;
+    }
   }
   double l = 0.0;
   int h = 0;
@@ -358,12 +404,89 @@ inline bool pr_overlap(const void* a, size_t na, const void* b, size_t nb) {
   return pa < pb + nb && pb < pa + na;
 }
 
+constexpr int PR_MAX_HEADS = 32;
+
+inline size_t probe_head_ws(int m, int d, int c) { return align_up(probe_layout(m, d, c).total, 16); }
+
+// The launches of a step (grads) or a score over `heads` classifiers; the arguments have been checked.  head_stride: floats
+// between consecutive heads of w / b / dw / db; ws_stride: floats between consecutive heads' workspaces (both unused with 1 head)
+inline int probe_run(hipStream_t st, bool grads, const float* x, const int32_t* rows, const int64_t* labels, const float* mean,
+                     const float* inv_std, const float* w, const float* b, size_t head_stride, int heads, int m, int n, int d, int c,
+                     float* loss, int32_t* hits, float* dw, float* db, void* ws) {
+  const ProbeWs lay = probe_layout(m, d, c);
+  const size_t ws_stride = align_up(lay.total, 16) / sizeof(float);
+  char* base = reinterpret_cast<char*>(ws);
+  float* g = reinterpret_cast<float*>(base + lay.g);
+  float* row_loss = reinterpret_cast<float*>(base + lay.row_loss);
+  int* row_hit = reinterpret_cast<int*>(base + lay.row_hit);
+  float* dbp = reinterpret_cast<float*>(base + lay.dbp);
+  float* partial = reinterpret_cast<float*>(base + lay.partial);
+  const int cpad = probe_cpad(c);
+  int vec = probe_vec(d, x, w, mean, inv_std);
+  const size_t lds = (size_t)PR_TM * c * sizeof(float);
+  if (!grads) {
+    hipLaunchKernelGGL(probe_logits_kernel<PR_SCORE>, dim3(cdiv(m, PR_TM), heads), dim3(256), lds, st, x, rows, labels, mean, inv_std,
+                       w, b, head_stride, ws_stride, m, n, d, c, cpad, vec, 1.f / (float)m, g, row_loss, row_hit, 0, nullptr, nullptr);
+    CSTP_LAUNCH_CHECK();
+    hipLaunchKernelGGL(probe_fold_kernel, dim3(1, heads), dim3(256), 0, st, partial, 1, (size_t)0, 0, (float*)nullptr, dbp, c,
+                       (float*)nullptr, row_loss, row_hit, m, loss, hits, head_stride, ws_stride);
+    CSTP_LAUNCH_CHECK();
+    return 0;
+  }
+  const int rps = (int)align_up((size_t)cdiv(m, probe_slices(m, d, c)), PR_GR);
+  const int ns = cdiv(m, rps);                                            // <= probe_slices: no slice is left without rows
+  float* out = ns > 1 ? partial : dw;
+  if ((d & 3) == 0 && pr_aligned16(out)) vec |= 8;                        // every head's out: both strides are multiples of 4 floats
+  hipLaunchKernelGGL(probe_logits_kernel<PR_STEP>, dim3(cdiv(m, PR_TM), heads), dim3(256), lds, st, x, rows, labels, mean, inv_std, w,
+                     b, head_stride, ws_stride, m, n, d, c, cpad, vec, 1.f / (float)m, g, row_loss, row_hit, 0, nullptr, nullptr);
+  CSTP_LAUNCH_CHECK();
+  hipLaunchKernelGGL(probe_wgrad_kernel, dim3(cdiv(d, PR_GT), cdiv(c, PR_GT), ns * heads), dim3(256), 0, st, x, rows, mean, inv_std, g,
+                     m, n, d, c, cpad, vec, rps, ns, ws_stride, ns > 1 ? ws_stride : head_stride, out, dbp);
+  CSTP_LAUNCH_CHECK();
+  const size_t cd = (size_t)c * d;
+  const int fold_blocks = ns > 1 ? (int)((cd + 255) / 256) : 0;
+  hipLaunchKernelGGL(probe_fold_kernel, dim3(fold_blocks + 1, heads), dim3(256), 0, st, partial, ns, cd, fold_blocks, dw, dbp, c, db,
+                     row_loss, row_hit, m, loss, hits, head_stride, ws_stride);
+  CSTP_LAUNCH_CHECK();
+  return 0;
+}
+
+// the checks the two sweep entry points share (dw == nullptr: score); 0 or the error code
+inline int probe_sweep_check(const float* w, const float* b, int64_t head_stride, int heads, int m, int n, int d, int c,
+                             const int32_t* rows, const float* dw, const float* db, const void* ws, size_t ws_bytes) {
+  CSTP_REQUIRE(heads >= 1 && heads <= PR_MAX_HEADS, "heads must be in 1..32");
+  CSTP_REQUIRE(c >= 2 && c <= PR_MAX_C, "c must be in 2..1024");
+  CSTP_REQUIRE(probe_shape_ok(m, n, d, c), "bad shape");
+  CSTP_REQUIRE(rows != nullptr || m <= n, "m must not exceed n without a row list");
+  const int64_t wn = ((int64_t)c * d + 3) & ~(int64_t)3;
+  CSTP_REQUIRE(head_stride > 0 && (head_stride & 3) == 0 && head_stride >= wn + c,
+               "head stride must be a multiple of 4 floats and at least pad4(c d) + c");
+  if (dw != nullptr) {
+    const size_t wb = (size_t)c * d * sizeof(float), bb = (size_t)c * sizeof(float);
+    for (int i = 0; i < heads; ++i)
+      for (int j = 0; j < heads; ++j) {
+        const float *dwi = dw + (size_t)i * head_stride, *dbi = db + (size_t)i * head_stride;
+        const float *wj = w + (size_t)j * head_stride, *bj = b + (size_t)j * head_stride;
+        CSTP_REQUIRE(!pr_overlap(dwi, wb, wj, wb) && !pr_overlap(dwi, wb, bj, bb) && !pr_overlap(dbi, bb, wj, wb) &&
+                         !pr_overlap(dbi, bb, bj, bb), "dw / db must not alias w / b of any head");
+      }
+  }
+  CSTP_REQUIRE(pr_aligned16(ws), "workspace must be 16-byte aligned");
+  CSTP_REQUIRE(ws_bytes >= (size_t)heads * probe_head_ws(m, d, c), "workspace too small");
+  return 0;
+}
+
 }  // namespace
 }  // namespace cstp
 
 extern "C" size_t cstp_probe_workspace_bytes(int32_t m, int32_t d, int32_t c) {
   if (!cstp::probe_shape_ok(m, 1, d, c)) return 0;
   return cstp::probe_layout(m, d, c).total;
+}
+
+extern "C" size_t cstp_probe_sweep_workspace_bytes(int32_t heads, int32_t m, int32_t d, int32_t c) {
+  if (heads < 1 || heads > cstp::PR_MAX_HEADS || !cstp::probe_shape_ok(m, 1, d, c)) return 0;
+  return (size_t)heads * cstp::probe_head_ws(m, d, c);
 }
 
 extern "C" int cstp_probe_step(void* stream, const float* x, const int32_t* rows, const int64_t* labels, const float* mean,
@@ -379,33 +502,32 @@ extern "C" int cstp_probe_step(void* stream, const float* x, const int32_t* rows
   CSTP_REQUIRE(!pr_overlap(dw, wb, w, wb) && !pr_overlap(dw, wb, b, bb) && !pr_overlap(db, bb, w, wb) && !pr_overlap(db, bb, b, bb),
                "dw / db must not alias w / b");
   CSTP_REQUIRE(pr_aligned16(ws), "workspace must be 16-byte aligned");
-  const ProbeWs lay = probe_layout(m, d, c);
-  CSTP_REQUIRE(ws_bytes >= lay.total, "workspace too small");
-  char* base = reinterpret_cast<char*>(ws);
-  float* g = reinterpret_cast<float*>(base + lay.g);
-  float* row_loss = reinterpret_cast<float*>(base + lay.row_loss);
-  int* row_hit = reinterpret_cast<int*>(base + lay.row_hit);
-  float* dbp = reinterpret_cast<float*>(base + lay.dbp);
-  float* partial = reinterpret_cast<float*>(base + lay.partial);
-  const int cpad = probe_cpad(c);
-  const int rps = (int)align_up((size_t)cdiv(m, probe_slices(m, d, c)), PR_GR);
-  const int ns = cdiv(m, rps);                                            // <= probe_slices: no slice is left without rows
-  float* out = ns > 1 ? partial : dw;
-  int vec = probe_vec(d, x, w, mean, inv_std);
-  if ((d & 3) == 0 && pr_aligned16(out)) vec |= 8;
-  hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(probe_logits_kernel<true>, dim3(cdiv(m, PR_TM)), dim3(256), (size_t)PR_TM * c * sizeof(float), st, x, rows,
-                     labels, mean, inv_std, w, b, m, n, d, c, cpad, vec, 1.f / (float)m, g, row_loss, row_hit, 0, nullptr, nullptr);
-  CSTP_LAUNCH_CHECK();
-  hipLaunchKernelGGL(probe_wgrad_kernel, dim3(cdiv(d, PR_GT), cdiv(c, PR_GT), ns), dim3(256), 0, st, x, rows, mean, inv_std, g, m, n,
-                     d, c, cpad, vec, rps, out, dbp);
-  CSTP_LAUNCH_CHECK();
-  const size_t cd = (size_t)c * d;
-  const int fold_blocks = ns > 1 ? (int)((cd + 255) / 256) : 0;
-  hipLaunchKernelGGL(probe_fold_kernel, dim3(fold_blocks + 1), dim3(256), 0, st, partial, ns, cd, fold_blocks, dw, dbp, c, db,
-                     row_loss, row_hit, m, loss, hits);
-  CSTP_LAUNCH_CHECK();
-  return 0;
+  CSTP_REQUIRE(ws_bytes >= probe_layout(m, d, c).total, "workspace too small");
+  return probe_run(as_stream(stream), true, x, rows, labels, mean, inv_std, w, b, 0, 1, m, n, d, c, loss, hits, dw, db, ws);
+}
+
+extern "C" int cstp_probe_sweep_step(void* stream, const float* x, const int32_t* rows, const int64_t* labels, const float* mean,
+                                     const float* inv_std, const float* w, const float* b, int64_t head_stride, int32_t heads,
+                                     int32_t m, int32_t n, int32_t d, int32_t c, float* loss, int32_t* hits, float* dw, float* db,
+                                     void* ws, size_t ws_bytes) {
+  using namespace cstp;
+  CSTP_REQUIRE(x != nullptr && labels != nullptr && w != nullptr && b != nullptr && loss != nullptr && hits != nullptr &&
+                   dw != nullptr && db != nullptr && ws != nullptr, "null argument");
+  if (const int rc = probe_sweep_check(w, b, head_stride, heads, m, n, d, c, rows, dw, db, ws, ws_bytes)) return rc;
+  return probe_run(as_stream(stream), true, x, rows, labels, mean, inv_std, w, b, (size_t)head_stride, heads, m, n, d, c, loss, hits,
+                   dw, db, ws);
+}
+
+extern "C" int cstp_probe_sweep_score(void* stream, const float* x, const int32_t* rows, const int64_t* labels, const float* mean,
+                                      const float* inv_std, const float* w, const float* b, int64_t head_stride, int32_t heads,
+                                      int32_t m, int32_t n, int32_t d, int32_t c, float* loss, int32_t* hits, void* ws,
+                                      size_t ws_bytes) {
+  using namespace cstp;
+  CSTP_REQUIRE(x != nullptr && labels != nullptr && w != nullptr && b != nullptr && loss != nullptr && hits != nullptr &&
+                   ws != nullptr, "null argument");
+  if (const int rc = probe_sweep_check(w, b, head_stride, heads, m, n, d, c, rows, nullptr, nullptr, ws, ws_bytes)) return rc;
+  return probe_run(as_stream(stream), false, x, rows, labels, mean, inv_std, w, b, (size_t)head_stride, heads, m, n, d, c, loss, hits,
+                   nullptr, nullptr, ws);
 }
 
 extern "C" int cstp_probe_predict(void* stream, const float* x, const float* mean, const float* inv_std, const float* w,
@@ -416,9 +538,9 @@ extern "C" int cstp_probe_predict(void* stream, const float* x, const float* mea
   CSTP_REQUIRE(n_top >= 1 && n_top <= PR_MAX_TOP, "n_top must be in 1..8");
   CSTP_REQUIRE(probe_shape_ok(n, n, d, c), "bad shape");
   const int vec = probe_vec(d, x, w, mean, inv_std);
-  hipLaunchKernelGGL(probe_logits_kernel<false>, dim3(cdiv(n, PR_TM)), dim3(256), (size_t)PR_TM * c * sizeof(float),
-                     as_stream(stream), x, nullptr, nullptr, mean, inv_std, w, b, n, n, d, c, probe_cpad(c), vec, 0.f, nullptr,
-                     nullptr, nullptr, n_top, pred, score);
+  hipLaunchKernelGGL(probe_logits_kernel<PR_PREDICT>, dim3(cdiv(n, PR_TM)), dim3(256), (size_t)PR_TM * c * sizeof(float),
+                     as_stream(stream), x, nullptr, nullptr, mean, inv_std, w, b, (size_t)0, (size_t)0, n, n, d, c, probe_cpad(c), vec,
+                     0.f, nullptr, nullptr, nullptr, n_top, pred, score);
   CSTP_LAUNCH_CHECK();
   return 0;
 }

@@ -2210,7 +2210,115 @@ def probe_predict(x, w, b, mean=None, inv_std=None, n_top=5):
     return pred, score
 
 
-KMEANS_MAX_ROWS, KMEANS_MAX_DIM, KMEANS_MAX_CLUSTERS, KMEANS_MAX_RESTARTS = 1 << 24, 4096, 4096, 32
+PROBE_MAX_HEADS = 32
+
+
+def _pad4(v: int) -> int:
+    return (v + 3) // 4 * 4
+
+
+def probe_head_views(arena: torch.Tensor, heads: int, c: int, d: int):
+    """(w [heads, c, d], b [heads, c]) as views of a flat fp32 arena of heads * seg floats, seg = pad4(c d) + pad4(c): head h's
+    W at h * seg and b at h * seg + pad4(c d) -- probe.fit's single-head layout, repeated."""
+    wn = _pad4(c * d)
+    seg = wn + _pad4(c)
+    if arena.dim() != 1 or not arena.is_contiguous() or arena.numel() < heads * seg:
+        raise _lib.CstpError("probe_head_views: the arena must be flat with at least %d floats, got %s" % (heads * seg, tuple(arena.shape)))
+    at = arena.storage_offset()                                   # as_strided counts from the storage, not from the view
+    return arena.as_strided((heads, c, d), (seg, d, 1), at), arena.as_strided((heads, c), (seg, 1), at + wn)
+
+
+def _probe_heads(op, w, b, what="w / b"):
+    """The head checks of the sweep calls on (w [G, c, d], b [G, c]) strided views -> (G, head stride in floats)."""
+    if w.dim() != 3 or b.dim() != 2 or w.shape[0] != b.shape[0]:
+        raise _lib.CstpError("%s: %s must be [heads, classes, features] and [heads, classes], got %s and %s"
+                             % (op, what, tuple(w.shape), tuple(b.shape)))
+    heads, c, d = w.shape
+    if not 1 <= heads <= PROBE_MAX_HEADS:
+        raise _lib.CstpError("%s: the number of heads must be in 1..%d, got %d" % (op, PROBE_MAX_HEADS, heads))
+    if w.dtype != torch.float32 or b.dtype != torch.float32:
+        raise _lib.CstpError("%s: %s must be float32, got %s and %s" % (op, what, w.dtype, b.dtype))
+    if c >= 1 and d >= 1 and (w.stride()[1:] != (d, 1) or b.stride(1) != 1):
+        raise _lib.CstpError("%s: every head of %s must be contiguous, strides are %s and %s" % (op, what, w.stride(), b.stride()))
+    if heads == 1:
+        return 1, _pad4(c * d) + _pad4(c)
+    if w.stride(0) != b.stride(0):
+        raise _lib.CstpError("%s: %s disagree on the head stride: %d and %d floats" % (op, what, w.stride(0), b.stride(0)))
+    stride = w.stride(0)
+    if stride % 4 or stride < _pad4(c * d) + c:
+        raise _lib.CstpError("%s: the head stride of %s must be a multiple of 4 floats and at least pad4(c d) + c = %d, got %d"
+                             % (op, what, _pad4(c * d) + c, stride))
+    return heads, stride
+
+
+def _probe_sweep(op, grads, x, labels, w, b, rows, mean, inv_std, out):
+    heads, stride = _probe_heads(op, w, b)
+    n, d, c = _probe_operands(op, x, w[0], b[0], mean, inv_std)
+    if labels.dim() != 1 or labels.shape[0] != n:
+        raise _lib.CstpError("%s: labels must be [%d], one per row of x, got %s" % (op, n, tuple(labels.shape)))
+    if labels.dtype != torch.int64:
+        raise _lib.CstpError("%s: labels must be int64, got %s" % (op, labels.dtype))
+    if rows is not None:
+        if rows.dim() != 1 or rows.shape[0] < 1:
+            raise _lib.CstpError("%s: rows must be a non-empty [m] vector, got %s" % (op, tuple(rows.shape)))
+        if rows.dtype != torch.int32:
+            raise _lib.CstpError("%s: rows must be int32, got %s" % (op, rows.dtype))
+    m = n if rows is None else rows.shape[0]
+    n_out = 4 if grads else 2
+    if out is not None:
+        if len(out) != n_out:
+            raise _lib.CstpError("%s: out must be %s" % (op, "(loss, hits, dw, db)" if grads else "(loss, hits)"))
+        for t, name, dtype in ((out[0], "out loss", torch.float32), (out[1], "out hits", torch.int32)):
+            if tuple(t.shape) != (heads,) or t.dtype != dtype:
+                raise _lib.CstpError("%s: %s must be %s of shape (%d,), got %s %s" % (op, name, dtype, heads, t.dtype, tuple(t.shape)))
+        if grads:
+            if tuple(out[2].shape) != tuple(w.shape) or tuple(out[3].shape) != tuple(b.shape):
+                raise _lib.CstpError("%s: out dw / db must have the shapes of w / b, got %s and %s"
+                                     % (op, tuple(out[2].shape), tuple(out[3].shape)))
+            if _probe_heads(op, out[2], out[3], "out dw / db")[1] != stride:
+                raise _lib.CstpError("%s: out dw / db must have the head stride of w / b (%d floats)" % (op, stride))
+    named = [(x, "x"), (labels, "labels"), (w, "w"), (b, "b"), (rows, "rows"), (mean, "mean"), (inv_std, "inv_std")]
+    if out is not None:
+        named += list(zip(out, ("out loss", "out hits", "out dw", "out db")))
+    _probe_devices(op, named)
+    for t, name in ((x, "x"), (labels, "labels"), (rows, "rows"), (mean, "mean"), (inv_std, "inv_std")) + \
+            (((out[0], "out loss"), (out[1], "out hits")) if out is not None else ()):
+        if t is not None:
+            _probe_c(op, t, name)
+    lib = _lib.load()
+    if out is None:
+        out = (torch.empty(heads, dtype=torch.float32, device=x.device), torch.empty(heads, dtype=torch.int32, device=x.device))
+        if grads:
+            arena = torch.zeros(heads * stride, dtype=torch.float32, device=x.device)
+            off = _pad4(c * d)
+            out += (arena.as_strided((heads, c, d), (stride, d, 1), 0), arena.as_strided((heads, c), (stride, 1), off))
+    ws = _workspace(x.device, lib.cstp_probe_sweep_workspace_bytes(heads, m, d, c))
+    if grads:
+        check(lib.cstp_probe_sweep_step(_stream(), x.data_ptr(), _ptr(rows), labels.data_ptr(), _ptr(mean), _ptr(inv_std),
+                                        w.data_ptr(), b.data_ptr(), stride, heads, m, n, d, c, out[0].data_ptr(), out[1].data_ptr(),
+                                        out[2].data_ptr(), out[3].data_ptr(), ws.data_ptr(), ws.numel()), "cstp_probe_sweep_step")
+    else:
+        check(lib.cstp_probe_sweep_score(_stream(), x.data_ptr(), _ptr(rows), labels.data_ptr(), _ptr(mean), _ptr(inv_std),
+                                         w.data_ptr(), b.data_ptr(), stride, heads, m, n, d, c, out[0].data_ptr(), out[1].data_ptr(),
+                                         ws.data_ptr(), ws.numel()), "cstp_probe_sweep_score")
+    return out
+
+
+def probe_sweep_step(x, labels, w, b, rows=None, mean=None, inv_std=None, out=None):
+    """probe_step for G <= 32 classifiers on the same batch in the same three launches (include/cstp_hip.h: cstp_probe_sweep_step):
+    w [G, c, d] and b [G, c] are strided views of one arena (probe_head_views) that agree on the head stride -> (loss [G] fp32,
+    hits [G] int32, dw [G, c, d], db [G, c]), head g's slices holding the bits probe_step gives for (w[g], b[g]) alone.  ``out`` =
+    (loss, hits, dw, db) preallocated, dw / db at the stride of w / b and not aliasing them: then nothing is allocated."""
+    return _probe_sweep("probe_sweep_step", True, x, labels, w, b, rows, mean, inv_std, out)
+
+
+def probe_sweep_score(x, labels, w, b, rows=None, mean=None, inv_std=None, out=None):
+    """Loss and hit count of every head on the gathered rows, no gradients: two launches, the bits of probe_sweep_step's first two
+    results (cstp_probe_sweep_score) -> (loss [G] fp32, hits [G] int32); ``out`` = (loss, hits) preallocated."""
+    return _probe_sweep("probe_sweep_score", False, x, labels, w, b, rows, mean, inv_std, out)
+
+
+KMEANS_MAX_ROWS,KMEANS_MAX_DIM, KMEANS_MAX_CLUSTERS, KMEANS_MAX_RESTARTS = 1 << 24, 4096, 4096, 32
 
 
 def _kmeans_operands(op, x, cent):

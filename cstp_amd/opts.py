@@ -66,6 +66,16 @@ Additions (all optional, defaults reproduce the reference):
   --probe_wd        its weight decay on the weight matrix, >= 0 (default 0; decoupled with adam, coupled with sgd)
   --probe_optimizer adam | sgd (momentum 0.9) (default adam); the number of classes is --n_finetune_classes; the defaults are
                     conventional choices, not tuned on real data (every other driver ignores all five)
+  --probe_lrs       linear_probe.py: one or more peak learning rates, each finite and > 0, no duplicates (default: not given =
+                    no sweep).  Given, the grid --probe_lrs x --probe_wds (lr-major, at most 32 points) is trained side by side
+                    on a stratified part of the TRAIN list and scored on the rest of it; the best point (validation top-1, then
+                    validation loss, then grid order) is refitted on the whole train list and scored on the test list
+  --probe_wds       the grid's weight decays, each finite and >= 0, no duplicates (default: not given = [--probe_wd])
+  --probe_val_fraction  the share of every class's train videos held out for the selection, in (0, 0.5] (default 0.2).
+                    --probe_wds and --probe_val_fraction are refused without --probe_lrs.  The three are absent from the parsed
+                    namespace when not given (opts.probe_grid reads them), so no driver's options dump changes.  The defaults of
+                    all eight probe flags remain conventional, untuned choices: no linear-probe accuracy of a trained encoder
+                    on real data has been measured with this code
   --cluster_k       k-means clustering evaluation (cluster.py): the number of clusters, >= 0; 0 = --n_finetune_classes (default 0)
   --cluster_iters   its Lloyd iterations per restart, exactly that many (no early stop: nothing is read back), >= 1 (default 50)
   --cluster_restarts  its k-means++ restarts, run side by side in one launch, 1..32; the best final score wins (default 10); the
@@ -233,6 +243,40 @@ def _probe_wd(text):
     return v
 
 
+PROBE_MAX_GRID = 32          # ops.PROBE_MAX_HEADS: the grid point is a grid dimension of the kernels
+PROBE_VAL_FRACTION = 0.2
+
+
+def _probe_val_fraction(text):
+    v = float(text)
+    if not (v > 0.0 and v <= 0.5):
+        raise argparse.ArgumentTypeError("--probe_val_fraction must be in (0, 0.5], got %r" % (text,))
+    return v
+
+
+def probe_grid(args):
+    """-> None without --probe_lrs, else (lrs, wds, val_fraction) with the defaults filled in: [--probe_wd] and 0.2."""
+    lrs = getattr(args, "probe_lrs", None)
+    if lrs is None:
+        return None
+    return list(lrs), list(getattr(args, "probe_wds", [args.probe_wd])), getattr(args, "probe_val_fraction", PROBE_VAL_FRACTION)
+
+
+def _check_probe_grid(parser, args):
+    lrs, wds = getattr(args, "probe_lrs", None), getattr(args, "probe_wds", None)
+    if lrs is None:
+        for flag in ("probe_wds", "probe_val_fraction"):
+            if hasattr(args, flag):
+                parser.error("--%s selects nothing without --probe_lrs" % flag)
+        return
+    for flag, vals in (("probe_lrs", lrs), ("probe_wds", wds or [])):
+        if len(set(vals)) != len(vals):
+            parser.error("--%s: duplicate values in %r" % (flag, vals))
+    if len(lrs) * len(wds or [0.0]) > PROBE_MAX_GRID:
+        parser.error("--probe_lrs x --probe_wds: %d grid points, at most %d train side by side"
+                     % (len(lrs) * len(wds or [0.0]), PROBE_MAX_GRID))
+
+
 CLUSTER_MAX_RESTARTS = 32    # ops.KMEANS_MAX_RESTARTS: the restart is a grid dimension of the kernels
 
 
@@ -278,6 +322,15 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--probe_lr", default=1e-3, type=_probe_lr, help="linear_probe.py: peak learning rate (cosine to 0), > 0")
     parser.add_argument("--probe_wd", default=0.0, type=_probe_wd, help="linear_probe.py: weight decay on the weight matrix, >= 0")
     parser.add_argument("--probe_optimizer", default="adam", choices=("adam", "sgd"), help="linear_probe.py: the update rule")
+    # absent from the namespace unless given: the options dump of every driver stays as it is (probe_grid reads them)
+    parser.add_argument("--probe_lrs", default=argparse.SUPPRESS, nargs="+", type=_probe_lr,
+                        help="linear_probe.py: sweep these peak learning rates (x --probe_wds, at most %d points) on a hold-out "
+                             "of the train list and refit the best" % PROBE_MAX_GRID)
+    parser.add_argument("--probe_wds", default=argparse.SUPPRESS, nargs="+", type=_probe_wd,
+                        help="linear_probe.py: the sweep's weight decays (default: --probe_wd); needs --probe_lrs")
+    parser.add_argument("--probe_val_fraction", default=argparse.SUPPRESS, type=_probe_val_fraction,
+                        help="linear_probe.py: share of each class's train videos held out for the selection, in (0, 0.5] "
+                             "(default %g); needs --probe_lrs" % PROBE_VAL_FRACTION)
     parser.add_argument("--cluster_k", default=0, type=_cluster_k,
                         help="cluster.py: number of k-means clusters, 0 = --n_finetune_classes")
     parser.add_argument("--cluster_iters", default=50, type=_cluster_iters,
@@ -289,7 +342,9 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 def parse_opts(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    _check_probe_grid(parser, args)
     if args.local_rank == -1 and "LOCAL_RANK" in os.environ:   # torchrun / torch.distributed.run
         args.local_rank = int(os.environ["LOCAL_RANK"])
     return args

@@ -781,6 +781,36 @@ int cstp_probe_step(void* stream, const float* x, const int32_t* rows, const int
 int cstp_probe_predict(void* stream, const float* x, const float* mean, const float* inv_std, const float* w, const float* b,
                        int32_t n, int32_t d, int32_t c, int32_t n_top, int32_t* pred, float* score);
 
+/* ---- linear-probe sweep: `heads` classifiers on the same batch in the same launches (csrc/probe.h) -------
+ * A head is one classifier (W_h [c][d], b_h [c]).  w and b point at head 0; head h lies head_stride floats further on, in both, and
+ * dw / db use the same stride.  probe.fit's arena layout is the intended one: seg = pad4(c d) + pad4(c) floats per head, W_h at
+ * h * seg, b_h at h * seg + pad4(c d) (pad4: up to a multiple of 4), head_stride = seg.  x, rows, labels, mean, inv_std are shared.
+ *
+ * cstp_probe_sweep_step: for every head h what cstp_probe_step returns for (W_h, b_h) alone on the same x, rows, labels, mean,
+ * inv_std -- loss[h], hits[h], dW_h, db_h -- BIT FOR BIT: the kernels are the single-head kernels with the head as a grid
+ * dimension (logits, fold) or a factor of one (dw: z = head * S + slice, S as for one head), so every fmaf chain, wave reduction,
+ * row slice and fold order is the single-head one.  Three launches whatever `heads` is, no atomics, no host read.
+ * cstp_probe_sweep_score: loss[h] and hits[h] only, the same bits; nothing of size [m][c] or [c][d] is written.  Two launches.
+ * Row indices outside [0, n) and labels outside [0, c) are treated as in cstp_probe_step, for every head.
+ *
+ * Workspace: head h owns bytes [h * round16(cstp_probe_workspace_bytes(m, d, c)), (h + 1) * the same), laid out as the single-head
+ * workspace; cstp_probe_sweep_workspace_bytes(heads, m, d, c) = heads * round16(cstp_probe_workspace_bytes(m, d, c)), 0 on a bad
+ * shape or heads outside 1..32.  Nothing is written outside loss [heads], hits [heads], the heads' dw / db extents ([c][d] and [c]
+ * floats each: the padding between heads is left alone) and that many bytes of ws; the score writes only the row-loss and row-hit
+ * parts of each head's workspace.
+ *
+ * Refused with a message before any HIP call: NULL among the required pointers (all but rows, mean, inv_std); heads outside
+ * 1..32; c outside 2..1024; a bad shape (as cstp_probe_step); m > n without rows; head_stride not a multiple of 4 or smaller than
+ * pad4(c d) + c; the dw / db extent of any head overlapping the w / b extent of any head; ws not 16-byte aligned or too small. */
+size_t cstp_probe_sweep_workspace_bytes(int32_t heads, int32_t m, int32_t d, int32_t c);
+int cstp_probe_sweep_step(void* stream, const float* x, const int32_t* rows, const int64_t* labels, const float* mean,
+                          const float* inv_std, const float* w, const float* b, int64_t head_stride, int32_t heads, int32_t m,
+                          int32_t n, int32_t d, int32_t c, float* loss, int32_t* hits, float* dw, float* db, void* ws,
+                          size_t ws_bytes);
+int cstp_probe_sweep_score(void* stream, const float* x, const int32_t* rows, const int64_t* labels, const float* mean,
+                           const float* inv_std, const float* w, const float* b, int64_t head_stride, int32_t heads, int32_t m,
+                           int32_t n, int32_t d, int32_t c, float* loss, int32_t* hits, void* ws, size_t ws_bytes);
+
 /* ---- fine-tuning regularisers: dropout and the stochastic-depth residual join (csrc/reg.h) -----------
  * Philox4x32-10 (Salmon et al., SC'11) on the host: out4 = Philox(ctr4, key2).  The function the dropout kernel evaluates,
  * exported so that its known answers can be checked without a device. */
