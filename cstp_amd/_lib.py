@@ -226,6 +226,11 @@ SIGNATURES = {
     "cstp_kmeans_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
     "cstp_kmeans_assign": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P, c_size_t]),
     "cstp_kmeans_update": (c_int32, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P]),
+    # label-free collapse metrics on cached features: feature Gram matrix and pairwise Gaussian potential (csrc/health.h)
+    "cstp_feat_gram_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "cstp_feat_gram": (c_int32, [_P, _P, c_int32, c_int32, _P, _P, _P, c_size_t]),
+    "cstp_pair_potential_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "cstp_pair_potential": (c_int32, [_P, _P, c_int32, c_int32, c_float, _P, _P, c_size_t]),
 }
 
 _lib = None

@@ -2,7 +2,7 @@
 // for R restarts at once, the restart being a grid dimension.  No [n][c] similarity table, no atomics, nothing read back.
 //
 //   1. kmeans_assign_kernel<VEC4>  block = 256 threads = 4 waves owns SQ_TQ = 64 rows of x and one restart, and walks that
-//      restart's centroids in tiles of SQ_TG = 128 -- simtopk_kernel's walk, staging and MFMA fragments, so a (row, centroid)
+//      restart's centroids in tiles of SQ_TG = 128 -- simtopk_kernel's walk, staging and MFMA fragments (sq_tile_scores), so a (row, centroid)
 //      similarity is the same fmaf chain over ascending features and holds the bits ops.sim_topk gives.  The 64 x 128 scores go
 //      over the operand image; a wave then owns 16 rows and lane l looks at centroids g0 + l and g0 + 64 + l: each lane keeps its
 //      own running (best, id) per row in registers, replaced only by a strictly larger value -- centroids arrive in ascending
@@ -48,11 +48,9 @@ kmeans_assign_kernel(const float* __restrict__ x, const float* __restrict__ cent
                      int* __restrict__ part_moved) {
   __shared__ float smem[SQ_SMEM];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lrow = lane >> 5, lcol = lane & 31;
   const int q0 = blockIdx.x * SQ_TQ, rs = blockIdx.y;
   const float* __restrict__ g = cent_all + (size_t)rs * c * d;
   const int gtiles = (c + SQ_TG - 1) / SQ_TG;
-  const int nchunk = (d + SQ_BK - 1) / SQ_BK;
 
   float bv[16];
   int bi[16];
@@ -62,82 +60,13 @@ kmeans_assign_kernel(const float* __restrict__ x, const float* __restrict__ cent
     bi[r] = -1;
   }
 
-  // staging: element e = tid + 256 p of a chunk is row e >> 3, features 4 (e & 7) .. + 3 (as simtopk_kernel)
   const int srow = tid >> 3, sc4 = (tid & 7) * 4;
   float4 qa[2], ga[4];
-  auto load_rows = [&](const float* base, int row0, int nrows, int c0, float4* dst, int np) __attribute__((always_inline)) {
-#pragma unroll
-    for (int p = 0; p < np; ++p) {
-      const int row = row0 + srow + 32 * p, col = c0 + sc4;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (row < nrows) {
-        const float* src = base + (size_t)row * d + col;
-        if (VEC4) {
-          if (col < d) v = *reinterpret_cast<const float4*>(src);   // d % 4 == 0: the four features are in or out together
-        } else {
-          if (col < d) v.x = src[0];
-          if (col + 1 < d) v.y = src[1];
-          if (col + 2 < d) v.z = src[2];
-          if (col + 3 < d) v.w = src[3];
-        }
-      }
-      dst[p] = v;
-    }
-  };
-  auto store_rows = [&](float* dst, int ld, const float4* src, int np) __attribute__((always_inline)) {
-#pragma unroll
-    for (int p = 0; p < np; ++p) {
-      float* o = dst + sc4 * ld + srow + 32 * p;
-      o[0] = src[p].x;
-      o[ld] = src[p].y;
-      o[2 * ld] = src[p].z;
-      o[3 * ld] = src[p].w;
-    }
-  };
-
-  load_rows(x, q0, n, 0, qa, 2);
-  load_rows(g, 0, c, 0, ga, 4);
+  sq_load_rows<VEC4>(x, q0, n, 0, d, srow, sc4, qa, 2);
+  sq_load_rows<VEC4>(g, 0, c, 0, d, srow, sc4, ga, 4);
   for (int t = 0; t < gtiles; ++t) {
     const int g0 = t * SQ_TG;
-    floatx16 acc0 = {0}, acc1 = {0};
-    store_rows(smem, SQ_LDA, qa, 2);                    // chunk 0 of this tile: loaded during the last chunk of the tile before
-    store_rows(smem + SQ_BK * SQ_LDA, SQ_LDB, ga, 4);
-    __syncthreads();
-    int buf = 0;
-    for (int kc = 0; kc < nchunk; ++kc) {
-      const bool have_next = kc + 1 < nchunk;
-      if (have_next) {
-        load_rows(x, q0, n, (kc + 1) * SQ_BK, qa, 2);
-        load_rows(g, g0, c, (kc + 1) * SQ_BK, ga, 4);
-      } else if (t + 1 < gtiles) {                      // in flight across the selection below
-        load_rows(x, q0, n, 0, qa, 2);
-        load_rows(g, g0 + SQ_TG, c, 0, ga, 4);
-      }
-      const float* Ab = smem + buf * SQ_BUF + lrow * SQ_LDA + lcol;
-      const float* Bb = smem + buf * SQ_BUF + SQ_BK * SQ_LDA + lrow * SQ_LDB + wave * 32 + lcol;
-#pragma unroll
-      for (int kk = 0; kk < SQ_BK; kk += 2) {
-        const float b = Bb[kk * SQ_LDB];
-        const float a0 = Ab[kk * SQ_LDA], a1 = Ab[kk * SQ_LDA + 32];
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b, acc1, 0, 0, 0);
-      }
-      if (have_next) {
-        float* nb = smem + (buf ^ 1) * SQ_BUF;
-        store_rows(nb, SQ_LDA, qa, 2);
-        store_rows(nb + SQ_BK * SQ_LDA, SQ_LDB, ga, 4);
-      }
-      __syncthreads();
-      buf ^= 1;
-    }
-    // every wave is past its last fragment read: the scores go over the operand image
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int m = (r & 3) + 8 * (r >> 2) + 4 * lrow;
-      smem[m * SQ_LDS + wave * 32 + lcol] = acc0[r];
-      smem[(m + 32) * SQ_LDS + wave * 32 + lcol] = acc1[r];
-    }
-    __syncthreads();
+    sq_tile_scores<VEC4>(smem, x, q0, n, g, g0, c, t + 1 < gtiles ? g0 + SQ_TG : -1, d, qa, ga);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int row = wave * 16 + r;

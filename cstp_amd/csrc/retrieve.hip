@@ -79,19 +79,108 @@ __device__ __forceinline__ void topk_push(float& sv, int& si, float v, int j, bo
   }
 }
 
+// ---- the walk that simtopk_kernel, kmeans_assign_kernel (kmeans.h) and pairpot_kernel (health.h) share ------------------------
+// staging: element e = tid + 256 p of a chunk is row e >> 3 (srow = tid >> 3), features 4 (e & 7) .. + 3 (sc4 = 4 (tid & 7))
+template <bool VEC4>
+__device__ __forceinline__ void sq_load_rows(const float* __restrict__ base, int row0, int nrows, int c0, int d, int srow, int sc4,
+                                             float4* dst, int np) {
+#pragma unroll
+  for (int p = 0; p < np; ++p) {
+    const int row = row0 + srow + 32 * p, c = c0 + sc4;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (row < nrows) {
+      const float* src = base + (size_t)row * d + c;
+      if (VEC4) {
+        if (c < d) v = *reinterpret_cast<const float4*>(src);   // d % 4 == 0: the four features are in or out together
+      } else {
+        if (c < d) v.x = src[0];
+        if (c + 1 < d) v.y = src[1];
+        if (c + 2 < d) v.z = src[2];
+        if (c + 3 < d) v.w = src[3];
+      }
+    }
+    dst[p] = v;
+  }
+}
+
+__device__ __forceinline__ void sq_store_rows(float* dst, int ld, const float4* src, int np, int srow, int sc4) {
+#pragma unroll
+  for (int p = 0; p < np; ++p) {
+    float* o = dst + sc4 * ld + srow + 32 * p;
+    o[0] = src[p].x;
+    o[ld] = src[p].y;
+    o[2 * ld] = src[p].z;
+    o[3 * ld] = src[p].w;
+  }
+}
+
+// one chunk of SQ_BK steps from an operand buffer ([k][64 A rows] at stride SQ_LDA, then [k][128 B rows] at stride SQ_LDB): wave w
+// multiplies the 64 A rows by B rows [32 w, 32 w + 32), k ascending
+__device__ __forceinline__ void sq_mma_chunk(const float* buf, int lrow, int lcol, int wave, floatx16& acc0, floatx16& acc1) {
+  const float* Ab = buf + lrow * SQ_LDA + lcol;
+  const float* Bb = buf + SQ_BK * SQ_LDA + lrow * SQ_LDB + wave * 32 + lcol;
+#pragma unroll
+  for (int kk = 0; kk < SQ_BK; kk += 2) {
+    const float b = Bb[kk * SQ_LDB];
+    const float a0 = Ab[kk * SQ_LDA], a1 = Ab[kk * SQ_LDA + 32];
+    acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b, acc0, 0, 0, 0);
+    acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b, acc1, 0, 0, 0);
+  }
+}
+
+// The 64 x 128 similarities of rows [q0, q0 + 64) of q and rows [g0, g0 + 128) of g -> smem[row * SQ_LDS + column], behind a
+// barrier.  On entry qa / ga hold chunk 0 of this tile; on exit chunk 0 of the tile at g_next (< 0: there is none), its loads
+// still in flight.  The caller puts a barrier between its reads of the scores and the next call.
+template <bool VEC4>
+__device__ __forceinline__ void sq_tile_scores(float* smem, const float* __restrict__ q, int q0, int nq, const float* __restrict__ g,
+                                               int g0, int ng, int g_next, int d, float4* qa, float4* ga) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int lrow = lane >> 5, lcol = lane & 31;
+  const int srow = tid >> 3, sc4 = (tid & 7) * 4;
+  const int nchunk = (d + SQ_BK - 1) / SQ_BK;
+  floatx16 acc0 = {0}, acc1 = {0};
+  sq_store_rows(smem, SQ_LDA, qa, 2, srow, sc4);        // chunk 0 of this tile: loaded during the last chunk of the tile before
+  sq_store_rows(smem + SQ_BK * SQ_LDA, SQ_LDB, ga, 4, srow, sc4);
+  __syncthreads();
+  int buf = 0;
+  for (int kc = 0; kc < nchunk; ++kc) {
+    const bool have_next = kc + 1 < nchunk;
+    if (have_next) {
+      sq_load_rows<VEC4>(q, q0, nq, (kc + 1) * SQ_BK, d, srow, sc4, qa, 2);
+      sq_load_rows<VEC4>(g, g0, ng, (kc + 1) * SQ_BK, d, srow, sc4, ga, 4);
+    } else if (g_next >= 0) {                           // in flight across the caller's work on the scores
+      sq_load_rows<VEC4>(q, q0, nq, 0, d, srow, sc4, qa, 2);
+      sq_load_rows<VEC4>(g, g_next, ng, 0, d, srow, sc4, ga, 4);
+    }
+    sq_mma_chunk(smem + buf * SQ_BUF, lrow, lcol, wave, acc0, acc1);
+    if (have_next) {
+      float* nb = smem + (buf ^ 1) * SQ_BUF;
+      sq_store_rows(nb, SQ_LDA, qa, 2, srow, sc4);
+      sq_store_rows(nb + SQ_BK * SQ_LDA, SQ_LDB, ga, 4, srow, sc4);
+    }
+    __syncthreads();
+    buf ^= 1;
+  }
+  // every wave is past its last fragment read: the scores go over the operand image
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    const int m = (r & 3) + 8 * (r >> 2) + 4 * lrow;
+    smem[m * SQ_LDS + wave * 32 + lcol] = acc0[r];
+    smem[(m + 32) * SQ_LDS + wave * 32 + lcol] = acc1[r];
+  }
+  __syncthreads();
+}
+
 template <bool VEC4>
 __global__ void __launch_bounds__(256)
 simtopk_kernel(const float* __restrict__ q, const float* __restrict__ g, int nq, int ng, int d, int k, int exclude_self,
                int tiles_per_split, float* __restrict__ out_val, int* __restrict__ out_idx) {
   __shared__ float smem[SQ_SMEM];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lrow = lane >> 5, lcol = lane & 31;
   const int q0 = blockIdx.x * SQ_TQ;
   const int gtiles = (ng + SQ_TG - 1) / SQ_TG;
   const int t_begin = blockIdx.y * tiles_per_split;
   const int t_end = t_begin + tiles_per_split < gtiles ? t_begin + tiles_per_split : gtiles;
-  const int nchunk = (d + SQ_BK - 1) / SQ_BK;
-
   float lv[16];
   int li[16];
 #pragma unroll
@@ -100,84 +189,15 @@ simtopk_kernel(const float* __restrict__ q, const float* __restrict__ g, int nq,
     li[r] = -1;
   }
 
-  // staging: element e = tid + 256 p of a chunk is row e >> 3, features 4 (e & 7) .. + 3
   const int srow = tid >> 3, sc4 = (tid & 7) * 4;
   float4 qa[2], ga[4];
-  auto load_rows = [&](const float* base, int row0, int nrows, int c0, float4* dst, int np) __attribute__((always_inline)) {
-#pragma unroll
-    for (int p = 0; p < np; ++p) {
-      const int row = row0 + srow + 32 * p, c = c0 + sc4;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (row < nrows) {
-        const float* src = base + (size_t)row * d + c;
-        if (VEC4) {
-          if (c < d) v = *reinterpret_cast<const float4*>(src);   // d % 4 == 0: the four features are in or out together
-        } else {
-          if (c < d) v.x = src[0];
-          if (c + 1 < d) v.y = src[1];
-          if (c + 2 < d) v.z = src[2];
-          if (c + 3 < d) v.w = src[3];
-        }
-      }
-      dst[p] = v;
-    }
-  };
-  auto store_rows = [&](float* dst, int ld, const float4* src, int np) __attribute__((always_inline)) {
-#pragma unroll
-    for (int p = 0; p < np; ++p) {
-      float* o = dst + sc4 * ld + srow + 32 * p;
-      o[0] = src[p].x;
-      o[ld] = src[p].y;
-      o[2 * ld] = src[p].z;
-      o[3 * ld] = src[p].w;
-    }
-  };
-
   if (t_begin < t_end) {
-    load_rows(q, q0, nq, 0, qa, 2);
-    load_rows(g, t_begin * SQ_TG, ng, 0, ga, 4);
+    sq_load_rows<VEC4>(q, q0, nq, 0, d, srow, sc4, qa, 2);
+    sq_load_rows<VEC4>(g, t_begin * SQ_TG, ng, 0, d, srow, sc4, ga, 4);
   }
   for (int t = t_begin; t < t_end; ++t) {
     const int g0 = t * SQ_TG;
-    floatx16 acc0 = {0}, acc1 = {0};
-    store_rows(smem, SQ_LDA, qa, 2);                    // chunk 0 of this tile: loaded during the last chunk of the tile before
-    store_rows(smem + SQ_BK * SQ_LDA, SQ_LDB, ga, 4);
-    __syncthreads();
-    int buf = 0;
-    for (int kc = 0; kc < nchunk; ++kc) {
-      const bool have_next = kc + 1 < nchunk;
-      if (have_next) {
-        load_rows(q, q0, nq, (kc + 1) * SQ_BK, qa, 2);
-        load_rows(g, g0, ng, (kc + 1) * SQ_BK, ga, 4);
-      } else if (t + 1 < t_end) {                       // in flight across the selection below
-        load_rows(q, q0, nq, 0, qa, 2);
-        load_rows(g, g0 + SQ_TG, ng, 0, ga, 4);
-      }
-      const float* Ab = smem + buf * SQ_BUF + lrow * SQ_LDA + lcol;
-      const float* Bb = smem + buf * SQ_BUF + SQ_BK * SQ_LDA + lrow * SQ_LDB + wave * 32 + lcol;
-#pragma unroll
-      for (int kk = 0; kk < SQ_BK; kk += 2) {
-        const float b = Bb[kk * SQ_LDB];
-        const float a0 = Ab[kk * SQ_LDA], a1 = Ab[kk * SQ_LDA + 32];
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b, acc1, 0, 0, 0);
-      }
-      if (have_next) {
-        float* nb = smem + (buf ^ 1) * SQ_BUF;
-        store_rows(nb, SQ_LDA, qa, 2);
-        store_rows(nb + SQ_BK * SQ_LDA, SQ_LDB, ga, 4);
-      }
-      __syncthreads();
-      buf ^= 1;
-    }
-    // every wave is past its last fragment read: the scores go over the operand image
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int m = (r & 3) + 8 * (r >> 2) + 4 * lrow;
-      smem[m * SQ_LDS + wave * 32 + lcol] = acc0[r];
-      smem[(m + 32) * SQ_LDS + wave * 32 + lcol] = acc1[r];
-    }
-    __syncthreads();
+    sq_tile_scores<VEC4>(smem, q, q0, nq, g, g0, ng, t + 1 < t_end ? g0 + SQ_TG : -1, d, qa, ga);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int row = wave * 16 + r, i = q0 + row;
@@ -364,3 +384,4 @@ extern "C" int cstp_knn_vote(void* stream, const float* val, const int32_t* idx,
 #include "probe.h"  // the linear probe on cached features: cstp_probe_step, cstp_probe_predict
 #include "ntxq.h"   // NT-Xent with a queue of negatives: cstp_ntxq_forward, cstp_ntxq_backward, cstp_ntxq_push
 #include "kmeans.h"  // spherical k-means on cached features: cstp_kmeans_assign, cstp_kmeans_update
+#include "health.h"  // label-free collapse metrics on cached features: cstp_feat_gram, cstp_pair_potential

@@ -2414,6 +2414,61 @@ def kmeans_update(x, assign, cent, out=None):
     return cent_new, counts
 
 
+HEALTH_MAX_DIM = 4096
+
+
+def _health_operand(op, x):
+    """The checks of feat_gram / pair_potential on x [n, d] -> (x detached, n, d)."""
+    if x.dim() != 2:
+        raise _lib.CstpError("%s: x must be [rows, features], got %s" % (op, tuple(x.shape)))
+    if x.dtype != torch.float32:
+        raise _lib.CstpError("%s: x must be float32, got %s" % (op, x.dtype))
+    n, d = x.shape
+    if n < 1 or d < 1:
+        raise _lib.CstpError("%s: empty operand, x is %s" % (op, tuple(x.shape)))
+    if d > HEALTH_MAX_DIM or n * d >= 1 << 31:
+        raise _lib.CstpError("%s: at most %d features and fewer than 2^31 elements are served, got x %s"
+                             % (op, HEALTH_MAX_DIM, tuple(x.shape)))
+    _probe_devices(op, [(x, "x")])
+    x = x.detach()
+    _probe_c(op, x, "x")
+    return x, n, d
+
+
+def feat_gram(x):
+    """x [n, d] fp32 -> (gram [d, d] fp64, colsum [d] fp64): gram[a, b] = sum_i x[i, a] * x[i, b] and colsum[a] = sum_i x[i, a]
+    (include/cstp_hip.h: cstp_feat_gram).  Rows go in slabs of 32: one fp32 fmaf chain per pair and slab on the f32 MFMA, the
+    slabs added in fp64 in ascending order; gram equals its transpose bit for bit, two calls give equal bits, no atomics.  The
+    scratch (ceil(n / 1024) * d doubles) is private and exact.  No autograd."""
+    op = "feat_gram"
+    x, n, d = _health_operand(op, x)
+    lib = _lib.load()
+    ws = torch.empty(lib.cstp_feat_gram_workspace_bytes(n, d), dtype=torch.uint8, device=x.device)
+    gram = torch.empty((d, d), dtype=torch.float64, device=x.device)
+    colsum = torch.empty((d,), dtype=torch.float64, device=x.device)
+    check(lib.cstp_feat_gram(_stream(), x.data_ptr(), n, d, gram.data_ptr(), colsum.data_ptr(), ws.data_ptr(), ws.numel()),
+          "cstp_feat_gram")
+    return gram, colsum
+
+
+def pair_potential(x, t=2.0):
+    """x [n, d] fp32, rows L2-normalised by the caller, t > 0 -> rowsum [n] fp64: rowsum[i] = sum_{j != i} exp(2 t (s_ij - 1)) with
+    s_ij the bits of sim_topk's similarity -- for unit rows exp(-t |x_i - x_j|^2), the Gaussian potential of Wang & Isola's
+    uniformity (include/cstp_hip.h: cstp_pair_potential).  The gallery streams past resident row tiles as in sim_topk: the [n, n]
+    matrix never exists, the scratch is at most 32 doubles per row.  fp32 expf per pair, fp64 sums in a fixed order, row i's own
+    column left out by index; no atomics, equal bits on equal inputs.  No autograd."""
+    op = "pair_potential"
+    if isinstance(t, bool) or not isinstance(t, (int, float)) or not (t > 0.0 and 2.0 * t < 3.0e38):
+        raise _lib.CstpError("%s: t must be a finite positive number, got %r" % (op, t))
+    x, n, d = _health_operand(op, x)
+    lib = _lib.load()
+    ws = torch.empty(lib.cstp_pair_potential_workspace_bytes(n, d), dtype=torch.uint8, device=x.device)
+    rowsum = torch.empty((n,), dtype=torch.float64, device=x.device)
+    check(lib.cstp_pair_potential(_stream(), x.data_ptr(), n, d, float(t), rowsum.data_ptr(), ws.data_ptr(), ws.numel()),
+          "cstp_pair_potential")
+    return rowsum
+
+
 # ----------------------------------------------------------------------------------------------
 # flat-arena utilities (no autograd)
 # ----------------------------------------------------------------------------------------------

@@ -81,6 +81,14 @@ Additions (all optional, defaults reproduce the reference):
   --cluster_restarts  its k-means++ restarts, run side by side in one launch, 1..32; the best final score wins (default 10); the
                     seed is --manual_seed; the defaults are conventional choices, not tuned on real data (every other driver
                     ignores all three)
+  --health_every    main_byol.py: after every E-th epoch and after the last, rank 0 computes the label-free collapse metrics of
+                    the online encoder on the test-list videos (cstp_amd/health.py: std_ratio, erank, rankme, top1_share,
+                    uniformity, nn_sim), prints ``Health epoch N: ...`` and appends a JSON line to health.jsonl in the run's
+                    result folder (default 0 = off); the data sets and sizes of --knn_every; it extracts its own features even
+                    where --knn_every fires in the same epoch; the epoch log is unchanged
+  --health_t        the t of the uniformity term exp(-t |x_i - x_j|^2) (health.py, --health_every), finite and > 0 (default 2).
+                    Both are absent from the parsed namespace when not given (opts.health_opts reads them), so no driver's
+                    options dump changes; every driver but main_byol.py and health.py ignores them
 torchrun passes LOCAL_RANK through the environment instead of --local_rank; both are honoured.
 """
 from __future__ import annotations
@@ -277,6 +285,25 @@ def _check_probe_grid(parser, args):
                      % (len(lrs) * len(wds or [0.0]), PROBE_MAX_GRID))
 
 
+HEALTH_T = 2.0               # cstp_amd.health.DEFAULT_T: Wang & Isola's choice
+
+
+def _health_every(text):
+    return int(text)          # main_byol.check_health_opts refuses a negative value with the monitor's own message
+
+
+def _health_t(text):
+    t = float(text)
+    if not (t > 0.0 and t < float("inf")):
+        raise argparse.ArgumentTypeError("--health_t must be finite and > 0, got %r" % (text,))
+    return t
+
+
+def health_opts(args):
+    """-> (health_every, health_t) with the defaults filled in: 0 (off) and 2.0."""
+    return getattr(args, "health_every", 0), getattr(args, "health_t", HEALTH_T)
+
+
 CLUSTER_MAX_RESTARTS = 32    # ops.KMEANS_MAX_RESTARTS: the restart is a grid dimension of the kernels
 
 
@@ -338,6 +365,13 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--cluster_restarts", default=10, type=_cluster_restarts,
                         help="cluster.py: k-means++ restarts, 1..%d, the best final score wins (a conventional choice, not tuned "
                              "on real data)" % CLUSTER_MAX_RESTARTS)
+    # absent from the namespace unless given, like the probe grid: the options dump stays as it is (health_opts reads them)
+    parser.add_argument("--health_every", default=argparse.SUPPRESS, type=_health_every,
+                        help="main_byol.py: label-free collapse metrics of the online encoder on the test-list videos after every "
+                             "E-th epoch and after the last (0 = off, the default); runs its own feature extraction even when "
+                             "--knn_every fires in the same epoch")
+    parser.add_argument("--health_t", default=argparse.SUPPRESS, type=_health_t,
+                        help="health.py / --health_every: t of the uniformity term, finite and > 0 (default %g)" % HEALTH_T)
     return parser
 
 

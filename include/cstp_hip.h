@@ -906,6 +906,35 @@ int cstp_kmeans_assign(void* stream, const float* x, const float* cent, const in
 int cstp_kmeans_update(void* stream, const float* x, const int32_t* assign, const float* cent_in, int32_t n, int32_t d, int32_t c,
                        int32_t r, float* cent_out, int32_t* counts);
 
+/* ---- label-free collapse metrics on cached features (csrc/health.h, included from csrc/retrieve.hip) ----
+ * x [n][d] fp32 rows, FINITE.  Two reductions that cstp_amd/health.py turns into rank, spread and uniformity figures; neither
+ * builds an [n][n] tensor nor uses an atomic, and two calls on equal inputs give equal bits.
+ *
+ * cstp_feat_gram: gram [d][d] fp64 and colsum [d] fp64,
+ *   gram[a][b] = sum_i x[i][a] * x[i][b]: the rows are dealt in slabs of 32; inside a slab the pair (a, b) is ONE fp32 fmaf chain
+ *                over ascending i (v_mfma_f32_32x32x2_f32), the slab partials are widened and added in fp64 in ascending slab order.
+ *                gram[a][b] and gram[b][a] are equal bit for bit (the two chains multiply the same factors).
+ *   colsum[a]  = sum_i x[i][a] in fp64: parts of 1024 rows, each added in ascending row order, the parts in ascending order.
+ *   The answer is a function of (x, n, d): no grid or split choice enters it.  Two launches.  Workspace: ceil(n / 1024) * d doubles
+ *   + 256 bytes = cstp_feat_gram_workspace_bytes(n, d).
+ *
+ * cstp_pair_potential: rowsum [n] fp64 for rows L2-normalised by the caller and t > 0,
+ *   rowsum[i] = sum_{j != i} expf(2 t (s_ij - 1)),  s_ij = sum_f x[i][f] * x[j][f] with the bits of cstp_simtopk's similarity (one
+ *               fmaf chain over ascending features), the accurate expf, the diagonal left out BY INDEX (duplicates of row i count).
+ *   Every term is widened to fp64.  The gallery tiles of 128 rows are dealt into S = at most 32 segments of ceil(tiles / 32)
+ *   tiles, a function of n alone; inside a segment lane l of a wave adds columns l, 64 + l of its tiles in ascending order and the
+ *   64 lanes go through one fixed tree; a second launch adds the S segment sums of a row in ascending order.  How many segments a
+ *   block walks (the gallery split of the grid, more blocks with few row tiles) changes no bit.  Workspace: S * n doubles + 256
+ *   bytes = cstp_pair_potential_workspace_bytes(n, d) <= 32 * 8 * n + 4096.
+ *
+ * Limits, refused with a message before any HIP call, nothing touched: n >= 1, 1 <= d <= 4096, n * d < 2^31; a NULL pointer; t not
+ * finite or <= 0; gram, colsum, rowsum or ws not 8-byte aligned; ws too small.  The workspace functions are pure host functions (0
+ * on a bad shape).  d need not be a multiple of 4 and x need not be 16-byte aligned (then it is staged by scalar loads). */
+size_t cstp_feat_gram_workspace_bytes(int32_t n, int32_t d);
+int cstp_feat_gram(void* stream, const float* x, int32_t n, int32_t d, double* gram, double* colsum, void* ws, size_t ws_bytes);
+size_t cstp_pair_potential_workspace_bytes(int32_t n, int32_t d);
+int cstp_pair_potential(void* stream, const float* x, int32_t n, int32_t d, float t, double* rowsum, void* ws, size_t ws_bytes);
+
 #ifdef __cplusplus
 }
 #endif

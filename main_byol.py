@@ -25,11 +25,16 @@ epoch and after the last one rank 0 classifies labelled test videos by weighted 
 --knn_t) under model.eval() + no_grad, the other ranks wait in a barrier, and training goes on unchanged (KnnMonitor).
 New: --ntxent_queue K (default 0 = off) gives the NT-Xent term (--ntxent_weight) K extra negatives per row: a FIFO queue of past
 online projections, normalised, identical on every rank, not checkpointed (cstp_amd.ntxent, csrc/ntxq.h).
+New: --health_every E (default 0 = off) watches for collapse without labels: after every E-th epoch and after the last one rank 0
+computes std_ratio, erank, rankme, top1_share, uniformity and nn_sim of the ONLINE encoder's features of the test-list videos
+(cstp_amd.health, --health_t), prints ``Health epoch N: ...`` and appends a JSON line to health.jsonl beside the epoch log; the
+epoch log and every other output line stay as they are (HealthMonitor).
 """
 from __future__ import annotations
 
 import argparse
 import builtins
+import json
 import os
 import random
 import time
@@ -40,11 +45,11 @@ import torch.distributed as dist
 from torch.utils.data import DataLoader
 from torch.utils.data.distributed import DistributedSampler
 
-from cstp_amd import knn, retrieval, sampler as clip_sampler
+from cstp_amd import health, knn, retrieval, sampler as clip_sampler
 from cstp_amd.model import generate_model
 from cstp_amd.ntxent import NTXentLoss
 from cstp_amd.optim import build_optimizer
-from cstp_amd.opts import parse_opts
+from cstp_amd.opts import health_opts, parse_opts
 from cstp_amd.scheduler import CosineAnnealingWarmupRestarts
 from cstp_amd.synthetic import SyntheticClips
 from cstp_amd.train import LaggedScalars, PretrainStep
@@ -83,6 +88,25 @@ def check_knn_opts(opts):
     except ValueError:
         raise ValueError("--knn_every %d with --sample_size %d: the monitor reads whole videos as the video test does, and its "
                          "ClipScale serves --sample_size 112 and 224 only" % (every, opts.sample_size)) from None
+
+
+def check_health_opts(opts):
+    """Refuses what the --health_every monitor cannot serve -- what check_knn_opts refuses: it reads the same whole-video sets;
+    called before any device work.  0 = off: nothing to check."""
+    every, _ = health_opts(opts)
+    if every < 0:
+        raise ValueError("--health_every takes 0 (off) or a positive number of epochs, got %d" % every)
+    if every == 0:
+        return
+    if opts.dataset not in KnnMonitor.SETS:
+        raise ValueError("--health_every %d with --dataset %s: the health monitor reads the whole test-list videos of --dataset "
+                         "synthetic_video and UcfRepreBYOLSpPre, the labelled sets of the k-NN monitor (their labels are "
+                         "ignored; --dataset synthetic is random clips without videos)" % (every, opts.dataset))
+    try:
+        clip_sampler.short_side(opts.sample_size)
+    except ValueError:
+        raise ValueError("--health_every %d with --sample_size %d: the monitor reads whole videos as the video test does, and "
+                         "its ClipScale serves --sample_size 112 and 224 only" % (every, opts.sample_size)) from None
 
 
 def check_ntxent_queue_opts(opts):
@@ -135,7 +159,44 @@ class KnnMonitor:
             retrieval.close_video_sets(*self.loaders)
 
 
-def train_BYOL(epoch, loader, step_fn, optimizer, opts, train_logger, knn_monitor=None):
+class HealthMonitor:
+    """--health_every: ``monitor(epoch)`` after every E-th epoch and after the last.  Rank 0 computes the label-free collapse
+    metrics of the online encoder on the test-list videos (cstp_amd.health.evaluate: eval mode, no_grad, the mode restored),
+    prints ``Health epoch N: ...`` and appends the JSON line to ``path``; under DDP every rank then meets in a barrier.  It
+    extracts its own features also where KnnMonitor fires in the same epoch.  Like that monitor it draws from no random generator
+    and updates no buffer."""
+
+    def __init__(self, opts, model, local_rank, path):
+        check_health_opts(opts)
+        self.every, self.t = health_opts(opts)
+        self.last, self.model, self.distributed, self.loader, self.path = opts.n_epochs, model, opts.distributed, None, path
+        if max(opts.rank, 0) == 0:
+            sets_opts = argparse.Namespace(**vars(opts))
+            sets_opts.device = torch.device("cuda", local_rank)
+            train_list, self.loader = retrieval.build_video_sets(sets_opts, KnnMonitor.SETS[opts.dataset])
+            retrieval.close_video_sets(train_list)          # only the test list is watched
+            del train_list
+            print("Health monitor: {} videos, t = {}".format(len(self.loader), self.t))
+
+    def __call__(self, epoch):
+        if epoch % self.every != 0 and epoch != self.last:
+            return None
+        res = None
+        if self.loader is not None:
+            res = dict(health.evaluate(self.model, self.loader, self.t), epoch=epoch)
+            print("Health epoch {}: {}".format(epoch, health.format_line(res)))
+            with open(self.path, "a") as f:
+                f.write(json.dumps(res) + "\n")
+        if self.distributed:
+            dist.barrier()
+        return res
+
+    def close(self):
+        if self.loader is not None:
+            retrieval.close_video_sets(self.loader)
+
+
+def train_BYOL(epoch, loader, step_fn, optimizer, opts, train_logger, knn_monitor=None, health_monitor=None):
     meters = {k: AverageMeter() for k in ("batch", "data", "loss", "loss_byol", "loss_pred_spa", "loss_pred_tem",
                                           "loss_pred_pb", "loss_pred_rot")}
     dev = torch.device("cuda", opts.local_rank)
@@ -178,6 +239,8 @@ def train_BYOL(epoch, loader, step_fn, optimizer, opts, train_logger, knn_monito
     if last is not None:
         log_line(last)
     acc = knn_monitor(epoch) if knn_monitor is not None else None      # every rank calls it: it ends in a barrier under DDP
+    if health_monitor is not None:
+        health_monitor(epoch)
     if opts.local_rank == 0:
         row = {k: meters[k].avg for k in LOG_COLUMNS if k in meters}
         row.update({"epoch": epoch, "acc": acc, "lr": float("{:.5f}".format(optimizer.param_groups[-1]["lr"]))})
@@ -252,6 +315,8 @@ def main_worker(local_rank, opts):
     step_fn = PretrainStep(model, optimizer, opts.loss_weight, task=opts.task, clip_grad_norm=opts.clip_grad_norm,
                            ntxent=criterion_ctr, ntxent_weight=opts.ntxent_weight)
     knn_monitor = KnnMonitor(opts, model, local_rank) if getattr(opts, "knn_every", 0) > 0 else None
+    health_monitor = HealthMonitor(opts, model, local_rank, os.path.join(log_path, "health.jsonl")) \
+        if health_opts(opts)[0] > 0 else None
     if opts.task in ("r_byol", "loss_com"):
         print("Start to train BYOL CoCLR data augmentation pre-trained model!")
         for epoch in range(begin_epoch, opts.n_epochs + 1):
@@ -259,10 +324,12 @@ def main_worker(local_rank, opts):
             if sampler is not None:
                 sampler.set_epoch(epoch)
             model.train()
-            train_BYOL(epoch, loader, step_fn, optimizer, opts, train_logger, knn_monitor)
+            train_BYOL(epoch, loader, step_fn, optimizer, opts, train_logger, knn_monitor, health_monitor)
             scheduler.step()
     if knn_monitor is not None:
         knn_monitor.close()
+    if health_monitor is not None:
+        health_monitor.close()
     if opts.distributed:
         dist.barrier()
         dist.destroy_process_group()
@@ -270,6 +337,7 @@ def main_worker(local_rank, opts):
 
 def main(opts):
     check_knn_opts(opts)
+    check_health_opts(opts)
     check_ntxent_queue_opts(opts)
     torch.manual_seed(opts.manual_seed)
     np.random.seed(opts.manual_seed)
