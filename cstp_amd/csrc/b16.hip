@@ -1488,7 +1488,7 @@ extern "C" int cstp_b16_bn_forward_train(void* stream, const uint16_t* x, const 
     return 0;
   }
   double* part = reinterpret_cast<double*>(ws);
-  const bool v8 = (s % 8) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(residual)) & 15) == 0;
+  const bool v8 = (s % 8) == 0 && al16(x) && al16(y) && al16(residual);
   const dim3 rgrid(c, groups * ns);
   if (v8) hipLaunchKernelGGL((b16_bn_reduce_kernel<0, true>), rgrid, dim3(256), 0, st, x, x, x, nullptr, nullptr, part, npg, c, s, ns, 0, nullptr);
   else hipLaunchKernelGGL((b16_bn_reduce_kernel<0, false>), rgrid, dim3(256), 0, st, x, x, x, nullptr, nullptr, part, npg, c, s, ns, 0, nullptr);
@@ -1520,8 +1520,7 @@ extern "C" int cstp_b16_bn_backward(void* stream, const uint16_t* x, const uint1
   }
   double* part = reinterpret_cast<double*>(ws);
   const float2* ss = reinterpret_cast<const float2*>(scale_shift);
-  const bool v8 = (s % 8) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(dy) |
-                                    reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(dresidual)) & 15) == 0;
+  const bool v8 = (s % 8) == 0 && al16(x) && al16(y) && al16(dy) && al16(dx) && al16(dresidual);
   const dim3 rgrid(c, groups * ns);
   if (v8) hipLaunchKernelGGL((b16_bn_reduce_kernel<1, true>), rgrid, dim3(256), 0, st, x, y, dy, save_mean, save_invstd, part, npg, c, s, ns, relu, ss);
   else hipLaunchKernelGGL((b16_bn_reduce_kernel<1, false>), rgrid, dim3(256), 0, st, x, y, dy, save_mean, save_invstd, part, npg, c, s, ns, relu, ss);
@@ -1540,7 +1539,7 @@ extern "C" int cstp_b16_bn_forward_eval(void* stream, const uint16_t* x, const u
                                         int32_t s, float eps, int32_t relu) {
   CSTP_REQUIRE(x && y && gamma && beta && running_mean && running_var, "null argument");
   CSTP_REQUIRE(n > 0 && c > 0 && s > 0, "bad shape");
-  const bool v8 = (s % 8) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(residual)) & 15) == 0;
+  const bool v8 = (s % 8) == 0 && al16(x) && al16(y) && al16(residual);
   const int chunks = cdiv(s, B16_UNROLL * 256 * (v8 ? 8 : 1));
   const dim3 agrid((unsigned)((size_t)n * c * chunks));
   if (v8) hipLaunchKernelGGL((b16_bn_eval_kernel<true>), agrid, dim3(256), 0, as_stream(stream), x, residual, y, gamma, beta, running_mean, running_var, c, s, eps, relu, chunks);

@@ -28,10 +28,6 @@ __device__ __forceinline__ float4 ld4_last(const float* p) {
 }
 
 
-// the float4 / non-temporal-vector kernels take 16-byte accesses at base + row * s: every row must be a multiple of 4 floats AND
-// every tensor of the call 16-byte aligned (a contiguous view at a 4-byte storage offset is not); a null pointer is not accessed
-static inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 static inline int bn_nsplit(int n, int c) {
   int ns = cdiv(2048, c);
   if (ns > n) ns = n;
@@ -225,16 +221,10 @@ constexpr int BN_UNROLL = 4;    // vectors per thread per block
 // consumer convolution's 2xf16-split operand scale (cstp_conv3d_*_am).  Every wave stores its own maximum into a slot of the
 // workspace (no atomics: same-address atomics execute at the memory side and serialise) and a one-block kernel folds the
 // slots into the caller's cell.
-__device__ __forceinline__ unsigned abs_bits(float v) { return __builtin_bit_cast(unsigned, v) & 0x7fffffffu; }
 __device__ __forceinline__ unsigned umax4(unsigned m, const float4& v) {
   unsigned a = abs_bits(v.x), b = abs_bits(v.y), c = abs_bits(v.z), d = abs_bits(v.w);
   a = a > b ? a : b; c = c > d ? c : d; a = a > c ? a : c;
   return m > a ? m : a;
-}
-__device__ __forceinline__ unsigned wave_umax(unsigned mx) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) { const unsigned o = (unsigned)__shfl_xor((int)mx, off, 64); mx = mx > o ? mx : o; }
-  return mx;
 }
 __device__ __forceinline__ void absmax_slot(unsigned mx, unsigned* slots) {
   mx = wave_umax(mx);

@@ -30,6 +30,9 @@ inline int fail(const char* fmt, const char* a = "", long b = 0, long c = 0) {
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// the 16-byte vector kernels take 16-byte accesses at base + row * s: every row must be a multiple of the vector width AND every
+// tensor of the call 16-byte aligned (a contiguous view at a 4-byte storage offset is not); a null pointer is not accessed
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // ---- device-side reductions (wave = 64 lanes) -------------------------------------------
 template <typename T>
@@ -58,6 +61,14 @@ __device__ __forceinline__ T block_sum(T v, T* smem /* >= 16 entries */) {
   if (wave == 0) r = wave_sum(r);
   __syncthreads();
   return r;
+}
+
+// ---- absmax by-products: fp32 bits with the sign cleared order like the magnitudes -----------
+__device__ __forceinline__ unsigned abs_bits(float v) { return __builtin_bit_cast(unsigned, v) & 0x7fffffffu; }
+__device__ __forceinline__ unsigned wave_umax(unsigned mx) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) { const unsigned o = (unsigned)__shfl_xor((int)mx, off, 64); mx = mx > o ? mx : o; }
+  return mx;
 }
 
 // ---- scalar bf16 <-> fp32 (bf16 travels as unsigned short) --------------------------------

@@ -28,7 +28,6 @@ __device__ __forceinline__ int gate_branch(const GateSet& gs, int ch) {
   return i;
 }
 
-__device__ __forceinline__ unsigned gate_abs_bits(float v) { return __builtin_bit_cast(unsigned, v) & 0x7fffffffu; }
 __device__ __forceinline__ unsigned gate_umax(unsigned a, unsigned b) { return a > b ? a : b; }
 
 constexpr int GATE_WAVES = 4;              // waves (rows in flight) per 256-thread block
@@ -93,14 +92,14 @@ __global__ void __launch_bounds__(256) gate_apply_kernel(GateSet gs, int rows, i
         const float4 v = x4[j];
         const float4 o = make_float4(gv * v.x, gv * v.y, gv * v.z, gv * v.w);
         y4[j] = o;
-        mx = gate_umax(mx, gate_umax(gate_umax(gate_abs_bits(o.x), gate_abs_bits(o.y)),
-                                     gate_umax(gate_abs_bits(o.z), gate_abs_bits(o.w))));
+        mx = gate_umax(mx, gate_umax(gate_umax(abs_bits(o.x), abs_bits(o.y)),
+                                     gate_umax(abs_bits(o.z), abs_bits(o.w))));
       }
     } else {
       for (int j = lane; j < s; j += 64) {
         const float o = gv * x[j];
         yr[j] = o;
-        mx = gate_umax(mx, gate_abs_bits(o));
+        mx = gate_umax(mx, abs_bits(o));
       }
     }
   }
@@ -222,7 +221,6 @@ __global__ void __launch_bounds__(256) gate_dx_kernel(GateSet gs, int rows, int 
   }
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // validates the branch table and fills the kernel-argument set; vec4: every row starts on a 16-byte boundary
 int make_set(const cstp_gate_branch* br, int nb, int n, int s, bool bwd, GateSet* gs, bool* vec4) {

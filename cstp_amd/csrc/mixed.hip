@@ -270,13 +270,7 @@ __device__ __forceinline__ int bnc_branch(const BncSet& bs, int ch) {
   return i;
 }
 
-__device__ __forceinline__ unsigned bnc_abs_bits(float v) { return __builtin_bit_cast(unsigned, v) & 0x7fffffffu; }
 __device__ __forceinline__ unsigned bnc_umax(unsigned a, unsigned b) { return a > b ? a : b; }
-__device__ __forceinline__ unsigned bnc_wave_umax(unsigned mx) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = bnc_umax(mx, (unsigned)__shfl_xor((int)mx, o, 64));
-  return mx;
-}
 
 constexpr int BNC_WAVES = 4;
 constexpr int BNC_APPLY_MAX_BLOCKS = 2048;
@@ -385,19 +379,19 @@ __global__ void __launch_bounds__(256) bnc_apply_kernel(BncSet bs, int rows, int
         v.x = v.x * sc + sh; v.y = v.y * sc + sh; v.z = v.z * sc + sh; v.w = v.w * sc + sh;
         v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
         y4[j] = v;
-        mx = bnc_umax(mx, bnc_umax(bnc_umax(bnc_abs_bits(v.x), bnc_abs_bits(v.y)), bnc_umax(bnc_abs_bits(v.z), bnc_abs_bits(v.w))));
+        mx = bnc_umax(mx, bnc_umax(bnc_umax(abs_bits(v.x), abs_bits(v.y)), bnc_umax(abs_bits(v.z), abs_bits(v.w))));
       }
     } else {
       for (int j = lane; j < s; j += 64) {
         float v = x[j] * sc + sh;
         v = fmaxf(v, 0.f);
         yr[j] = v;
-        mx = bnc_umax(mx, bnc_abs_bits(v));
+        mx = bnc_umax(mx, abs_bits(v));
       }
     }
   }
   if (cell == nullptr) return;        // grid-uniform
-  mx = bnc_wave_umax(mx);
+  mx = wave_umax(mx);
   if (lane == 0) red[wave] = mx;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -489,7 +483,7 @@ __global__ void __launch_bounds__(256) bnc_bwd_apply_kernel(BncSet bs, int rows,
         o.z = kk * (g.z - mb - (v.z - mu) * is * mg);
         o.w = kk * (g.w - mb - (v.w - mu) * is * mg);
         o4[j] = o;
-        m = bnc_umax(m, bnc_umax(bnc_umax(bnc_abs_bits(o.x), bnc_abs_bits(o.y)), bnc_umax(bnc_abs_bits(o.z), bnc_abs_bits(o.w))));
+        m = bnc_umax(m, bnc_umax(bnc_umax(abs_bits(o.x), abs_bits(o.y)), bnc_umax(abs_bits(o.z), abs_bits(o.w))));
       }
     } else {
       for (int j = lane; j < s; j += 64) {
@@ -498,7 +492,7 @@ __global__ void __launch_bounds__(256) bnc_bwd_apply_kernel(BncSet bs, int rows,
         if (!((v * sc + sh) > 0.f)) g = 0.f;
         const float o = kk * (g - mb - (v - mu) * is * mg);
         dx[j] = o;
-        m = bnc_umax(m, bnc_abs_bits(o));
+        m = bnc_umax(m, abs_bits(o));
       }
     }
 #pragma unroll
@@ -507,7 +501,7 @@ __global__ void __launch_bounds__(256) bnc_bwd_apply_kernel(BncSet bs, int rows,
   }
 #pragma unroll
   for (int j = 0; j < CSTP_BNC_MAX_BRANCHES; ++j) {
-    const unsigned a = bnc_wave_umax(mx[j]);
+    const unsigned a = wave_umax(mx[j]);
     if (lane == 0) red[wave][j] = a;
   }
   __syncthreads();
@@ -518,7 +512,6 @@ __global__ void __launch_bounds__(256) bnc_bwd_apply_kernel(BncSet bs, int rows,
   }
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 // mode 0: train forward, 1: eval forward, 2: backward
 int make_bnc(const cstp_bnc_branch* br, int nb, int n, int s, int groups, int mode, BncSet* bs, bool* vec4, bool* need_stats) {

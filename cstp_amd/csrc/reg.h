@@ -63,7 +63,6 @@ __device__ __forceinline__ unsigned short reg_f2bf(float a) {
   return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
 }
 __device__ __forceinline__ unsigned reg_umax(unsigned a, unsigned b) { return a > b ? a : b; }
-__device__ __forceinline__ unsigned reg_abs_bits(float v) { return __builtin_bit_cast(unsigned, v) & 0x7fffffffu; }
 
 __device__ __forceinline__ float droppath_one(float s, float z, float r) { return fmaxf(fmaf(s, z, r), 0.f); }
 
@@ -89,12 +88,12 @@ droppath_fwd_kernel(const T* __restrict__ z, const T* __restrict__ res, const fl
         o.x = droppath_one(s, zv.x, rv.x); o.y = droppath_one(s, zv.y, rv.y);
         o.z = droppath_one(s, zv.z, rv.z); o.w = droppath_one(s, zv.w, rv.w);
         *reinterpret_cast<float4*>(yb + 4 * i) = o;
-        mx = reg_umax(reg_umax(mx, reg_abs_bits(o.x)), reg_abs_bits(o.y));
-        mx = reg_umax(reg_umax(mx, reg_abs_bits(o.z)), reg_abs_bits(o.w));
+        mx = reg_umax(reg_umax(mx, abs_bits(o.x)), abs_bits(o.y));
+        mx = reg_umax(reg_umax(mx, abs_bits(o.z)), abs_bits(o.w));
       } else if constexpr (sizeof(T) == 4) {
         const float o = droppath_one(s, zb[i], rb[i]);
         yb[i] = o;
-        mx = reg_umax(mx, reg_abs_bits(o));
+        mx = reg_umax(mx, abs_bits(o));
       } else if constexpr (W == 8) {
         const uint4 zv = *reinterpret_cast<const uint4*>(zb + 8 * i);
         const uint4 rv = *reinterpret_cast<const uint4*>(rb + 8 * i);
