@@ -231,6 +231,9 @@ SIGNATURES = {
     "cstp_feat_gram": (c_int32, [_P, _P, c_int32, c_int32, _P, _P, _P, c_size_t]),
     "cstp_pair_potential_workspace_bytes": (c_size_t, [c_int32, c_int32]),
     "cstp_pair_potential": (c_int32, [_P, _P, c_int32, c_int32, c_float, _P, _P, c_size_t]),
+    # few-shot episodic evaluation on cached features: N-way K-shot cosine nearest-centroid episodes (csrc/fewshot.h)
+    "cstp_fewshot_episodes": (c_int32, [_P, _P, c_int32, _P, c_int32, c_int32, _P, _P, c_int32, c_int32, c_int32, POINTER(c_int32),
+                                        c_int32, _P, _P, _P]),
 }
 
 _lib = None

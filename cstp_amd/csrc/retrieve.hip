@@ -385,3 +385,4 @@ extern "C" int cstp_knn_vote(void* stream, const float* val, const int32_t* idx,
 #include "ntxq.h"   // NT-Xent with a queue of negatives: cstp_ntxq_forward, cstp_ntxq_backward, cstp_ntxq_push
 #include "kmeans.h"  // spherical k-means on cached features: cstp_kmeans_assign, cstp_kmeans_update
 #include "health.h"  // label-free collapse metrics on cached features: cstp_feat_gram, cstp_pair_potential
+#include "fewshot.h"  // few-shot episodic evaluation on cached features: cstp_fewshot_episodes

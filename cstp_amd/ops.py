@@ -2469,6 +2469,95 @@ def pair_potential(x, t=2.0):
     return rowsum
 
 
+FEWSHOT_MAX_WAY, FEWSHOT_MAX_QUERY, FEWSHOT_MAX_SLOTS = 20, 32, 320
+FEWSHOT_MAX_SHOTS, FEWSHOT_MAX_SHOT = 4, 16
+FEWSHOT_MAX_DIM, FEWSHOT_MAX_EPISODES = 8192, 1 << 20
+
+
+def fewshot_shots(shots):
+    """The shot counts of a call as a tuple: 1..4 ints, strictly ascending, each in 1..16 (CstpError otherwise)."""
+    try:
+        ks = tuple(shots)
+    except TypeError:
+        ks = None
+    if not ks or len(ks) > FEWSHOT_MAX_SHOTS or any(isinstance(k, bool) or not isinstance(k, int) for k in ks):
+        raise _lib.CstpError("fewshot_episodes: shots must be 1..%d ints, got %r" % (FEWSHOT_MAX_SHOTS, shots))
+    if any(not 1 <= k <= FEWSHOT_MAX_SHOT for k in ks) or any(b <= a for a, b in zip(ks, ks[1:])):
+        raise _lib.CstpError("fewshot_episodes: shots must be strictly ascending in 1..%d, got %r" % (FEWSHOT_MAX_SHOT, ks))
+    return ks
+
+
+def _fewshot_table(t, name, rows):
+    """An index table as the kernel wants it.  A CPU table is range-checked against ``rows`` here; a device table is trusted."""
+    if t.dtype != torch.int32:
+        raise _lib.CstpError("fewshot_episodes: %s must be int32, got %s" % (name, t.dtype))
+    _probe_c("fewshot_episodes", t, name)
+    if not t.is_cuda:
+        lo, hi = int(t.min()), int(t.max())
+        if lo < 0 or hi >= rows:
+            raise _lib.CstpError("fewshot_episodes: %s holds rows %d..%d, the features have rows 0..%d" % (name, lo, hi, rows - 1))
+    return t
+
+
+def fewshot_episodes(xs, xq, sup_idx, qry_idx, n_query, shots, want_pred=False, want_score=False):
+    """N-way K-shot episodes under the cosine nearest-centroid classifier (include/cstp_hip.h: cstp_fewshot_episodes).
+    xs [ns, d], xq [nq, d] fp32 with rows L2-normalised by the caller; sup_idx [E, N, Kmax] int32 rows of xs, qry_idx [E, N, Q]
+    int32 rows of xq, the query in slot (c, j) belonging to class slot c; shots = (k_1 < ... < k_S), k_S = Kmax.  For every shot
+    count the prototype of a class slot is the sum of its FIRST k support columns, a query's score its dot product with the
+    prototype over the prototype's norm (0 for a zero prototype), its prediction the best slot, the lowest on a tie.
+    -> hits [S, E] int32 on the device (queries answered with their own slot), then pred [S, E, N * Q] int32 and
+    score [S, E, N * Q, N] fp32 where asked for.  One launch, one block per episode, no gather tensor, no atomics; equal bits on
+    equal inputs, and an episode's bits do not depend on the other episodes or shot counts of the call.
+    Index tables given as CPU tensors are range-checked against ns / nq and then uploaded; tables already on the device ARE TAKEN
+    AS VALID -- the kernel reads whatever row they name.  No autograd."""
+    op = "fewshot_episodes"
+    ks = fewshot_shots(shots)
+    for t, name in ((xs, "xs"), (xq, "xq")):
+        if t.dim() != 2:
+            raise _lib.CstpError("%s: %s must be [rows, features], got %s" % (op, name, tuple(t.shape)))
+        if t.dtype != torch.float32:
+            raise _lib.CstpError("%s: %s must be float32, got %s" % (op, name, t.dtype))
+    (ns, d), nq = xs.shape, xq.shape[0]
+    if xq.shape[1] != d:
+        raise _lib.CstpError("%s: xs has %d features, xq %d" % (op, d, xq.shape[1]))
+    if ns < 1 or nq < 1 or d < 1:
+        raise _lib.CstpError("%s: empty operand, xs %s and xq %s" % (op, tuple(xs.shape), tuple(xq.shape)))
+    if d > FEWSHOT_MAX_DIM:
+        raise _lib.CstpError("%s: at most %d features are served, got %d" % (op, FEWSHOT_MAX_DIM, d))
+    if sup_idx.dim() != 3 or qry_idx.dim() != 3:
+        raise _lib.CstpError("%s: sup_idx must be [episodes, ways, shots] and qry_idx [episodes, ways, queries], got %s and %s"
+                             % (op, tuple(sup_idx.shape), tuple(qry_idx.shape)))
+    e, n, kmax = sup_idx.shape
+    if isinstance(n_query, bool) or not isinstance(n_query, int) or not 1 <= n_query <= FEWSHOT_MAX_QUERY:
+        raise _lib.CstpError("%s: n_query must be an int in 1..%d, got %r" % (op, FEWSHOT_MAX_QUERY, n_query))
+    if tuple(qry_idx.shape) != (e, n, n_query):
+        raise _lib.CstpError("%s: qry_idx must be %s beside sup_idx %s and n_query %d, got %s"
+                             % (op, (e, n, n_query), tuple(sup_idx.shape), n_query, tuple(qry_idx.shape)))
+    if kmax != ks[-1]:
+        raise _lib.CstpError("%s: sup_idx has %d support columns, the largest shot count is %d" % (op, kmax, ks[-1]))
+    if not 2 <= n <= FEWSHOT_MAX_WAY or n * n_query > FEWSHOT_MAX_SLOTS:
+        raise _lib.CstpError("%s: 2..%d ways and at most %d query slots are served, got %d ways x %d queries"
+                             % (op, FEWSHOT_MAX_WAY, FEWSHOT_MAX_SLOTS, n, n_query))
+    if not 1 <= e <= FEWSHOT_MAX_EPISODES:
+        raise _lib.CstpError("%s: 1..2^20 episodes are served, got %d" % (op, e))
+    sup_idx, qry_idx = _fewshot_table(sup_idx, "sup_idx", ns), _fewshot_table(qry_idx, "qry_idx", nq)
+    _probe_devices(op, [(xs, "xs"), (xq, "xq")])
+    xs, xq = xs.detach(), xq.detach()
+    _probe_c(op, xs, "xs")
+    _probe_c(op, xq, "xq")
+    sup_idx, qry_idx = sup_idx.to(xs.device), qry_idx.to(xs.device)
+    lib = _lib.load()
+    s = len(ks)
+    hits = torch.empty((s, e), dtype=torch.int32, device=xs.device)
+    pred = torch.empty((s, e, n * n_query), dtype=torch.int32, device=xs.device) if want_pred else None
+    score = torch.empty((s, e, n * n_query, n), dtype=torch.float32, device=xs.device) if want_score else None
+    check(lib.cstp_fewshot_episodes(_stream(), xs.data_ptr(), ns, xq.data_ptr(), nq, d, sup_idx.data_ptr(), qry_idx.data_ptr(), e, n,
+                                    n_query, (ctypes.c_int32 * s)(*ks), s, hits.data_ptr(), _ptr(pred), _ptr(score)),
+          "cstp_fewshot_episodes")
+    out = (hits,) + ((pred,) if want_pred else ()) + ((score,) if want_score else ())
+    return out[0] if len(out) == 1 else out
+
+
 # ----------------------------------------------------------------------------------------------
 # flat-arena utilities (no autograd)
 # ----------------------------------------------------------------------------------------------

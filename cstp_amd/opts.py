@@ -89,6 +89,17 @@ Additions (all optional, defaults reproduce the reference):
   --health_t        the t of the uniformity term exp(-t |x_i - x_j|^2) (health.py, --health_every), finite and > 0 (default 2).
                     Both are absent from the parsed namespace when not given (opts.health_opts reads them), so no driver's
                     options dump changes; every driver but main_byol.py and health.py ignores them
+  --fewshot_way     few-shot episodic evaluation (fewshot.py): classes per episode, 2..20 (default 5)
+  --fewshot_shot    its shot counts, one to four values in 1..16, strictly ascending (default 1 5); the counts are nested -- the
+                    K-shot prototype is the sum of the first K support videos of the same episode -- so they are paired
+  --fewshot_query   query videos per class and episode, 1..32, with way x query <= 320 (default 15)
+  --fewshot_episodes  random episodes, 1..2^20 (default 10000); accuracy is the mean over them, +- 1.96 std / sqrt(episodes)
+  --fewshot_seed    seed of the episode sampler's private generator, >= 0 (default 0): equal flags give equal episodes.
+                    Support videos come from the train list, queries from the test list (cstp_amd/fewshot.py, csrc/fewshot.h:
+                    one launch for all episodes).  All five are absent from the parsed namespace when not given
+                    (opts.fewshot_opts reads them), so no driver's options dump changes; every driver but fewshot.py ignores
+                    them.  The defaults are the literature's conventions, not tuned: no few-shot accuracy of a trained encoder
+                    on real data has been measured with this code
 torchrun passes LOCAL_RANK through the environment instead of --local_rank; both are honoured.
 """
 from __future__ import annotations
@@ -304,6 +315,37 @@ def health_opts(args):
     return getattr(args, "health_every", 0), getattr(args, "health_t", HEALTH_T)
 
 
+# ops.FEWSHOT_*: the limits of cstp_fewshot_episodes
+FEWSHOT_MAX_WAY, FEWSHOT_MAX_QUERY, FEWSHOT_MAX_SLOTS, FEWSHOT_MAX_SHOTS, FEWSHOT_MAX_SHOT, FEWSHOT_MAX_EPISODES = 20, 32, 320, 4, 16, 1 << 20
+FEWSHOT_DEFAULTS = (5, (1, 5), 15, 10000, 0)      # way, shots, queries per class, episodes, seed: the literature's conventions
+
+
+def _int_in(flag, lo, hi):
+    def parse(text):
+        v = int(text)
+        if not lo <= v <= hi:
+            raise argparse.ArgumentTypeError("--%s takes values in %d..%d, got %d" % (flag, lo, hi, v))
+        return v
+    return parse
+
+
+def fewshot_opts(args):
+    """-> (way, shots, queries per class, episodes, seed) with the defaults filled in: 5, (1, 5), 15, 10000, 0."""
+    way, shots, query, episodes, seed = FEWSHOT_DEFAULTS
+    return (getattr(args, "fewshot_way", way), tuple(getattr(args, "fewshot_shot", shots)), getattr(args, "fewshot_query", query),
+            getattr(args, "fewshot_episodes", episodes), getattr(args, "fewshot_seed", seed))
+
+
+def _check_fewshot(parser, args):
+    way, shots, query, _, _ = fewshot_opts(args)
+    if len(shots) > FEWSHOT_MAX_SHOTS:
+        parser.error("--fewshot_shot: at most %d shot counts, got %r" % (FEWSHOT_MAX_SHOTS, list(shots)))
+    if any(b <= a for a, b in zip(shots, shots[1:])):
+        parser.error("--fewshot_shot: the shot counts must be strictly ascending, got %r" % (list(shots),))
+    if way * query > FEWSHOT_MAX_SLOTS:
+        parser.error("--fewshot_way x --fewshot_query: %d query slots per episode, at most %d" % (way * query, FEWSHOT_MAX_SLOTS))
+
+
 CLUSTER_MAX_RESTARTS = 32    # ops.KMEANS_MAX_RESTARTS: the restart is a grid dimension of the kernels
 
 
@@ -372,6 +414,20 @@ def build_parser() -> argparse.ArgumentParser:
                              "--knn_every fires in the same epoch")
     parser.add_argument("--health_t", default=argparse.SUPPRESS, type=_health_t,
                         help="health.py / --health_every: t of the uniformity term, finite and > 0 (default %g)" % HEALTH_T)
+    # absent from the namespace unless given, like the health flags (fewshot_opts reads them)
+    parser.add_argument("--fewshot_way", default=argparse.SUPPRESS, type=_int_in("fewshot_way", 2, FEWSHOT_MAX_WAY),
+                        help="fewshot.py: classes per episode, 2..%d (default %d)" % (FEWSHOT_MAX_WAY, FEWSHOT_DEFAULTS[0]))
+    parser.add_argument("--fewshot_shot", default=argparse.SUPPRESS, nargs="+", type=_int_in("fewshot_shot", 1, FEWSHOT_MAX_SHOT),
+                        help="fewshot.py: one to %d shot counts in 1..%d, strictly ascending, nested within an episode (default 1 5)"
+                             % (FEWSHOT_MAX_SHOTS, FEWSHOT_MAX_SHOT))
+    parser.add_argument("--fewshot_query", default=argparse.SUPPRESS, type=_int_in("fewshot_query", 1, FEWSHOT_MAX_QUERY),
+                        help="fewshot.py: query videos per class and episode, 1..%d, way x query <= %d (default %d)"
+                             % (FEWSHOT_MAX_QUERY, FEWSHOT_MAX_SLOTS, FEWSHOT_DEFAULTS[2]))
+    parser.add_argument("--fewshot_episodes", default=argparse.SUPPRESS, type=_int_in("fewshot_episodes", 1, FEWSHOT_MAX_EPISODES),
+                        help="fewshot.py: random episodes, 1..2^20 (default %d; a convention of the literature, not tuned)"
+                             % FEWSHOT_DEFAULTS[3])
+    parser.add_argument("--fewshot_seed", default=argparse.SUPPRESS, type=_int_in("fewshot_seed", 0, (1 << 63) - 1),
+                        help="fewshot.py: seed of the episode sampler, >= 0 (default %d)" % FEWSHOT_DEFAULTS[4])
     return parser
 
 
@@ -379,6 +435,7 @@ def parse_opts(argv=None):
     parser = build_parser()
     args = parser.parse_args(argv)
     _check_probe_grid(parser, args)
+    _check_fewshot(parser, args)
     if args.local_rank == -1 and "LOCAL_RANK" in os.environ:   # torchrun / torch.distributed.run
         args.local_rank = int(os.environ["LOCAL_RANK"])
     return args

@@ -935,6 +935,31 @@ int cstp_feat_gram(void* stream, const float* x, int32_t n, int32_t d, double* g
 size_t cstp_pair_potential_workspace_bytes(int32_t n, int32_t d);
 int cstp_pair_potential(void* stream, const float* x, int32_t n, int32_t d, float t, double* rowsum, void* ws, size_t ws_bytes);
 
+/* ---- few-shot episodic evaluation on cached features (csrc/fewshot.h, included from csrc/retrieve.hip) --
+ * N-way K-shot episodes scored by the cosine nearest-centroid classifier ("ProtoNet with cosine" on frozen features).
+ * xs [ns][d], xq [nq][d] fp32, rows L2-normalised by the caller, FINITE.  sup_idx [E][N][Kmax] int32 rows of xs, qry_idx [E][N][Q]
+ * int32 rows of xq; the query in slot (c, j) belongs to class slot c.  shots [S] is a HOST array k_1 < ... < k_S, read before the
+ * launch, Kmax = k_S.  For episode e, shot count s and class slot c:
+ *   p = sum_{j < k_s} xs[sup_idx[e][c][j]]       the FIRST k_s support columns, added in column order: the shot counts are nested,
+ *                                                so the counts of one call are paired on the same episodes
+ *   score[s][e][q][c] = (xq[qry_idx[e][q]] . p) / sqrtf(p . p),  0.0f where p . p == 0
+ *   pred[s][e][q]     = the arg-max over c, the LOWEST slot on a tie
+ *   hits[s][e]        = the number of queries q with pred[s][e][q] == q / Q
+ * hits [S][E] int32 is always written; pred [S][E][N Q] int32 and score [S][E][N Q][N] fp32 may be NULL (the normal call: S * E
+ * integers are all that is stored).  fp32 throughout.  The features go in slices of 128; within a slice a dot product is 16 fmaf
+ * chains of 8 features (feature g, g + 16, ..., g + 112 of the slice in lane g) joined by one fixed tree, the slices are added in
+ * ascending order.  Every sum's order is a function of d alone: episode e has the same bits alone and among 2^20 others, shot count
+ * k the same bits alone and inside a list, and two calls on equal inputs give equal bits.  One launch, one 256-thread block per
+ * episode, no atomics, no workspace.  THE INDEX TABLES ARE TRUSTED: an entry outside 0..ns-1 / 0..nq-1 is an out-of-bounds read
+ * (ops.fewshot_episodes range-checks host tables before it uploads them); duplicates are fine.
+ * Limits, refused with a message before any HIP call, nothing touched: 2 <= N <= 20, 1 <= Q <= 32, N Q <= 320, 1 <= S <= 4, shots
+ * strictly ascending in 1..16, 1 <= d <= 8192, 1 <= E <= 2^20, ns, nq >= 1, a NULL among xs, xq, sup_idx, qry_idx, shots, hits.
+ * d need not be a multiple of anything and no pointer 16-byte aligned (rows are read by 4-byte loads, 256 or 64 contiguous bytes
+ * at a time). */
+int cstp_fewshot_episodes(void* stream, const float* xs, int32_t ns, const float* xq, int32_t nq, int32_t d,
+                          const int32_t* sup_idx, const int32_t* qry_idx, int32_t episodes, int32_t n_way, int32_t n_query,
+                          const int32_t* shots, int32_t n_shots, int32_t* hits, int32_t* pred, float* score);
+
 #ifdef __cplusplus
 }
 #endif
